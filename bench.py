@@ -1,6 +1,7 @@
 """Env-steps/s of the HIP quadrotor step (BASELINE.json metric), one process per GPU.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--task LeeLanded] [--num-envs 4096]
+                    [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...
 
 A "step" is one VecTask.step of the hot path (vec_task.py:313-359) over one batch
@@ -18,12 +19,21 @@ state in registers, writes every step's obs / rew / reset / time_outs into (K, N
 rollout storage, and reduces the rollout's finished-episode statistics in the same
 launch; when N > 1 those statistics are all-reduced over RCCL (asynchronously, a
 block of rollouts per collective) -- the single collective of the path.
-The same steps as one ``quad_step_kernel`` launch per step (the ``VecTask.step``
-call, ``ouz_step``) are measured beside it (``per_step_launch``).  Weak scaling:
-every rank simulates ``num_envs`` envs of the global id range.
+Weak scaling: every rank simulates ``num_envs`` envs of the global id range.
 
-Rank 0 prints ONE JSON line.  ``roofline`` prices the headline kernel at the bench
-workload from HIP events on its stream; ``roofline_sweep`` repeats the pricing at
+A plain run does what the headline needs and no more: it sets up, runs ``--warmup``
+steps, times exactly ``--steps`` steps, writes the last timed launch's outputs if
+``--dump-outputs DIR`` is given (the rollout storage and the episode statistics, the
+same from run to run for the same arguments, as ``DIR/<name>.npy``), and prints the
+line: ``value``, ``ms_per_step`` (wall milliseconds per timed step) and ``roofline``,
+which prices the headline kernel at the bench workload from the HIP events recorded
+around that same timed region.  Everything below runs only with ``--full``.
+
+``--full``: the same steps as one ``quad_step_kernel`` launch per step (the
+``VecTask.step`` call, ``ouz_step``) are measured beside the headline
+(``per_step_launch``), both paths' back-to-back kernel times are taken
+(``kernel_us_back_to_back``), and the side file (``--detail``) is written.
+Rank 0 prints ONE JSON line.  ``roofline_sweep`` repeats the roofline pricing at
 large N, where the state no longer fits the 256 MiB Infinity Cache (at
 4096 envs the whole state is cache-resident, so an HBM fraction there means little).
 ``configs`` carries the other single-GPU BASELINE configs (C, D and E's per-GPU
@@ -125,6 +135,13 @@ def parse():
     ap.add_argument("--launch-steps", type=int, default=MAX_LAUNCH_STEPS,
                     help="steps per fused rollout launch (<= 32): the env-only loop (train_vec.py:14-18) has no "
                          "rollout length of its own; 16 = the learners' T")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: the per-step launch path, back-to-back kernel times, the large-N "
+                         "roofline sweep, the other BASELINE configs, the CPU baselines (before the GPU starts) and "
+                         "the side file (--detail); a plain run times the headline steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step's launch handed its caller (rollout storage and episode "
+                         "statistics) as DIR/<name>.npy, float32 / float64, at most 64 MB")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-sweep", action="store_true")
     ap.add_argument("--no-configs", action="store_true", help="skip the other single-GPU BASELINE configs")
@@ -134,7 +151,7 @@ def parse():
                     help="rollouts whose return statistics share one all-reduce (N > 1)")
     ap.add_argument("--detail", default=os.path.join("gpurun_out", "bench_detail.json"),
                     help="side file of the full record (every roofline entry with its traffic detail, the sweep, "
-                         "the CPU table); the stdout line stays compact and names it")
+                         "the CPU table), written by a --full run; the stdout line stays compact and names it")
     return ap.parse_args()
 
 
@@ -613,6 +630,21 @@ class Runner:
             el = float(t.item())
         return el, gpu_us
 
+    def last_outputs(self, steps):
+        """What the last fused launch of a ``rollouts(steps)`` region handed its caller, copied on the device: the
+        launch's rollout storage rows (``rollout_*``: (k, N, ...) obs / rew / reset / time_outs), its last step's
+        row on its own (``obs`` / ``rew`` / ``reset`` / ``time_outs``) and the rollout's episode statistics
+        ([return sum, episode count, length sum], global when N > 1)."""
+        k = launch_sizes(steps, self.launch)[-1]
+        stats = self.red.result(self.n_roll - 1)
+        torch.cuda.synchronize(self.dev)
+        out = {}
+        for name, t in zip(("obs", "rew", "reset", "time_outs"), self.storage):
+            out["rollout_" + name] = t[:k].clone()
+            out[name] = t[k - 1].clone()
+        out["episode_stats"] = stats.clone()
+        return out
+
     def back_to_back_us(self, fused=True, launches=40):
         """GPU time per step of back-to-back launches queued behind a spin kernel (no host gap): kernel time
         plus the ~1 us dependent-launch boundary (MI355X_MICROARCH.md 'boundary' row)."""
@@ -635,14 +667,17 @@ class Runner:
         return s.elapsed_time(e) * 1e3 / steps
 
 
-def measure(task, n, dev, seed, rank, world, args, red, with_per_step=True):
-    """Headline-style measurement of one config: fused rollouts (timed), then the per-step launch path."""
+def measure(task, n, dev, seed, rank, world, args, red, with_per_step=True, keep_outputs=False):
+    """Headline-style measurement of one config: fused rollouts (timed), then (``with_per_step``) the per-step
+    launch path.  ``keep_outputs``: the last timed launch's outputs, copied right after the timed region."""
     run = Runner(task, n, dev, seed, rank, world, red, args.launch_steps)
     run.setup_timing(args.steps)
     run.rollouts(max(args.warmup, 1))
     el, gpu_us = run.timed(args.steps, world)
     out = {"value": n * world * args.steps / el, "ms_per_step": el / args.steps * 1e3, "kernel_us": gpu_us,
            "steps": args.steps}
+    if keep_outputs:
+        out["outputs"] = run.last_outputs(args.steps)
     if with_per_step:
         run.setup_timing(args.steps, fused=False)
         run.rollouts(max(args.warmup, 1), fused=False)
@@ -851,6 +886,33 @@ def write_detail(path, out):
         json.dump(out, fh, indent=1)
 
 
+DUMP_LIMIT_BYTES = 64 * 1000 * 1000   # --dump-outputs: all files together
+DUMP_SAMPLE_SEED = 0
+
+
+def write_outputs(path, outputs, n):
+    """``--dump-outputs``: every tensor of ``Runner.last_outputs`` as ``<name>.npy``, float64 statistics, float32
+    otherwise (reset / time_outs as 0 / 1).  If the arrays would exceed the limit, the same fixed, seeded sample of
+    envs is taken from each (ascending env ids, listed in ``env_index.npy``)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    per_env = sum(t.numel() // n * 4 for name, t in outputs.items() if name != "episode_stats")
+    budget = DUMP_LIMIT_BYTES - (1 << 20)    # headers, the statistics and the index
+    idx = None
+    if per_env * n > budget:
+        m = max(1, int(budget // (per_env + 8)))
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, size=m, replace=False))
+        np.save(os.path.join(path, "env_index.npy"), idx.astype(np.float64))
+    for name, t in outputs.items():
+        if name == "episode_stats":
+            a = t.to(torch.float64).cpu().numpy()
+        else:
+            if idx is not None:
+                t = t.index_select(1 if name.startswith("rollout_") else 0, torch.as_tensor(idx, device=t.device))
+            a = t.to(torch.float32).cpu().numpy()
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def split_timeouts():
     """Give-ups of the split-wave / output-wave LDS waits since the process started (quad_pv_split.h): 0 unless
     the protocol is broken, in which case the measured rollouts were wrong."""
@@ -868,7 +930,7 @@ def main():
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     cpu = None
-    if world == 1 and not args.no_cpu_baseline:   # forked workers: before anything initialises the GPU
+    if args.full and world == 1 and not args.no_cpu_baseline:   # forked workers: before anything initialises the GPU
         cpu = cpu_baseline_leg(args.task, args.num_envs, args.seed, args.cpu_seconds)
 
     from ouzelum_amd.distributed import ReturnAllReduce, init_from_env, rccl_comm_count
@@ -890,7 +952,8 @@ def main():
     # stream, double-buffered so the next rollouts' steps do not wait for it, and ARB rollouts' rows per
     # collective: one dist.all_reduce call costs ~20 us of host time (distributed.ReturnAllReduce)
     red = ReturnAllReduce(dev, batch=args.allreduce_batch)
-    run, res = measure(args.task, n, dev, args.seed, rank, world, args, red)
+    run, res = measure(args.task, n, dev, args.seed, rank, world, args, red, with_per_step=args.full,
+                       keep_outputs=bool(args.dump_outputs))
 
     if rank != 0:
         if world > 1:
@@ -900,9 +963,8 @@ def main():
 
     letter = TASK_CONFIG.get(args.task, "-")
     desc = CONFIGS[letter][2] if letter in CONFIGS else args.task
-    us_b2b = run.back_to_back_us(fused=True)
-    us_b2b_step = run.back_to_back_us(fused=False)
-    ps = res["per_step"]
+    if args.dump_outputs:
+        write_outputs(args.dump_outputs, res.pop("outputs"), n)
     backend = dist.get_backend() if world > 1 else None
     out = {
         "metric": METRIC, "value": round(res["value"], 1), "unit": "env-steps/s", "n_gpus": world,
@@ -927,16 +989,18 @@ def main():
         "roofline": {**roofline_entry("rollout", args.task, n, res["kernel_us"], run.launch, args.steps),
                      "kernel_us_source": "HIP events on the step stream around the timed region / steps "
                                          f"(rollout launches of up to {run.launch} steps, episode statistics fused)",
-                     "kernel_us_back_to_back": round(us_b2b, 3),
                      "regime": "latency-bound: 4096 envs' state is L2/MALL-resident, see roofline_sweep"},
-        "per_step_launch": {
+    }
+    if args.full:
+        ps = res["per_step"]
+        out["roofline"]["kernel_us_back_to_back"] = round(run.back_to_back_us(fused=True), 3)
+        out["per_step_launch"] = {
             "value": round(ps["value"], 1), "ms_per_step": round(ps["ms_per_step"], 5),
             "note": "the same steps as one quad_step_kernel launch per VecTask.step (ouz_step_n_stats: one C "
                     "call per rollout, episode statistics as a separate launch)",
             "roofline": {**roofline_entry("step", args.task, n, ps["kernel_us"]),
-                         "kernel_us_back_to_back": round(us_b2b_step, 3)}},
-    }
-    if world == 1:
+                         "kernel_us_back_to_back": round(run.back_to_back_us(fused=False), 3)}}
+    if args.full and world == 1:
         del run
         torch.cuda.empty_cache()
         if not args.no_sweep:
@@ -958,9 +1022,12 @@ def main():
             out["cpu_baseline"] = cpu
     torch.cuda.synchronize(dev)
     out["split_timeouts"] = split_timeouts()
-    out["detail"] = args.detail
+    out["detail"] = args.detail if args.full else None
+    if not args.full and any(a == "--detail" or a.startswith("--detail=") for a in sys.argv[1:]):
+        print("bench: --detail is written by a --full run only; no side file for this plain run", file=sys.stderr)
     try:
-        write_detail(args.detail, out)
+        if args.full:
+            write_detail(args.detail, out)
     except OSError as e:   # the line still prints; the side file is a convenience
         print(f"bench: could not write {args.detail}: {e}", file=sys.stderr)
         out["detail"] = None

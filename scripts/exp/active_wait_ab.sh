@@ -6,7 +6,7 @@ VALUES=${VALUES:-default 50 200 1000}
 for v in $VALUES; do
   for i in 1 2; do
     if [ "$v" = default ]; then unset ROC_ACTIVE_WAIT_TIMEOUT; else export ROC_ACTIVE_WAIT_TIMEOUT=$v; fi
-    timeout -k 10 200 python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-sweep --no-configs \
+    timeout -k 10 200 python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-sweep --no-configs \
       > gpurun_out/aw_${v}_$i.json 2>/dev/null || exit 1
     python3 - "$v" "gpurun_out/aw_${v}_$i.json" <<'PY'
 import json, sys

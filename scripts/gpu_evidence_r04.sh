@@ -29,10 +29,10 @@ stage() {   # summaries of this build into profiles/r04 on the box, so that its 
   for f in gpurun_out/valu_${TAG}_*_summary.json; do [ -e "$f" ] && cp "$f" profiles/r04/valu/; done
   return 0; }
 driver_bench() {
-  step bench_driver 400 python -u bench.py --gpus 1 --steps 20 --warmup 5 --detail "$OUT/bench_detail_driver.json"
+  step bench_driver 400 python -u bench.py --full --gpus 1 --steps 20 --warmup 5 --detail "$OUT/bench_detail_driver.json"
   export TMPDIR=/tmp
   step prof_driver 400 rocprofv3 --kernel-trace --stats -f csv -d "$R/$OUT/prof" -o run -- \
-    python3 -u bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-sweep --no-configs --detail "$OUT/bench_detail_prof.json"
+    python3 -u bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-sweep --no-configs --detail "$OUT/bench_detail_prof.json"
   tail -c 300 "$OUT/bench_driver.out"; echo; }
 if [ "$PART" = h ]; then
   bash scripts/gpu_roofline_evidence.sh "$TAG" rollout:LeeLanded:4096 step:LeeLanded:4096 > "$OUT/evidence_h.log" 2>&1 \
@@ -59,7 +59,7 @@ else
   bash scripts/gpu_roofline_evidence.sh "$TAG" > "$OUT/evidence_large.log" 2>&1 || { tail -n 20 "$OUT/evidence_large.log"; exit 1; }
   echo "evidence large-N ok"
   stage
-  step bench_default 500 python -u bench.py --detail "$OUT/bench_detail_default.json"
+  step bench_default 500 python -u bench.py --full --detail "$OUT/bench_detail_default.json"
   driver_bench
   tail -c 300 "$OUT/bench_default.out"; echo
 fi

@@ -8,6 +8,6 @@ timeout -k 10 900 python -u -m pytest -x -v --timeout 400 --timeout-method threa
   tests/test_dr_physical.py -m gpu "tests/test_gpu_learner.py::test_shipped_gemm_tuning_applies_on_this_box" \
   > gpurun_out/r06a/pytest.log 2>&1
 rc=$?; tail -25 gpurun_out/r06a/pytest.log; [ $rc -eq 0 ] || exit $rc
-timeout -k 10 300 python -u bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-sweep \
+timeout -k 10 300 python -u bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-sweep \
   --detail gpurun_out/r06a/bench_detail.json > gpurun_out/r06a/bench.out 2> gpurun_out/r06a/bench.err
 rc=$?; tail -c 1500 gpurun_out/r06a/bench.out; exit $rc

@@ -5,7 +5,7 @@ set -o pipefail
 O=gpurun_out/r06y
 mkdir -p $O
 for i in 1 2 3; do
-  timeout -k 10 400 python -u bench.py --gpus 1 --steps 20 --warmup 5 --detail $O/detail_$i.json > $O/bench_$i.out 2> $O/bench_$i.err || exit 1
+  timeout -k 10 400 python -u bench.py --full --gpus 1 --steps 20 --warmup 5 --detail $O/detail_$i.json > $O/bench_$i.out 2> $O/bench_$i.err || exit 1
   tail -n 1 $O/bench_$i.out | cut -c1-200
 done
 OUZ_DIST_BACKEND=gloo timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 \

@@ -17,9 +17,9 @@ def pytest_configure(config):
 
 @pytest.fixture(scope="session")
 def golden():
-    import numpy as np
+    from tests import golden_io
     d = os.path.join(ROOT, "tests", "golden")
 
-    def load(name):
-        return np.load(os.path.join(d, name))
+    def load(name):   # a fixture too large for one committed file is stored in parts (tests/golden_io.py)
+        return golden_io.load(os.path.join(d, name))
     return load

@@ -6,6 +6,7 @@ import os
 import numpy as np
 
 from oracle import quad_oracle as Q
+from tests import golden_io
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GLUE = {"ekf": "EKFLeeLanded", "ekf_flicker": "EKFLeeLanded", "lee": "LeeLanded", "ouz": "Ouzelum",
@@ -14,8 +15,7 @@ PLAT_KEYS = ("plat", "plat_heading", "traj_type", "traj_idx", "traj_sd")
 
 
 def load(name):
-    with np.load(os.path.join(ROOT, "tests", "golden", f"glue_{name}.npz")) as z:
-        return {k: z[k] for k in z.files}
+    return dict(golden_io.load(os.path.join(ROOT, "tests", "golden", f"glue_{name}.npz")))
 
 
 def oracle_config(name, fx, n=None):

@@ -52,6 +52,7 @@ sys.path.insert(0, ROOT)
 
 from oracle import philox as rng  # noqa: E402
 from oracle import quad_oracle as Q  # noqa: E402
+from tests import golden_io  # noqa: E402
 
 TASK_IDS = {"EKFLeeLanded": Q.TASK_EKF_LEE_LANDED, "LeeLanded": Q.TASK_LEE_LANDED, "Ouzelum": Q.TASK_OUZELUM,
             "Landing": Q.TASK_LANDING}
@@ -650,7 +651,7 @@ def main():
             os.chdir(cwd)
             torch.set_default_dtype(torch.float32)
     for k, v in res.items():
-        np.savez_compressed(os.path.join(HERE, f"glue_{k}.npz"), **v)
+        golden_io.save(os.path.join(HERE, f"glue_{k}.npz"), **v)   # in parts: each file under 1 MB
         print(k, {kk: vv.shape for kk, vv in v.items() if vv.ndim > 1})
 
 

@@ -41,6 +41,9 @@ import numpy as np
 import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
+
+from tests import golden_io  # noqa: E402
 
 
 def _load(name, path):
@@ -230,7 +233,7 @@ def gen_pv(ref):
                         f"s{seed}_trig_v": trig_v, f"s{seed}_x_f32ref": xs32.astype(np.float32),
                         f"s{seed}_P_f32ref": Ps32.astype(np.float32)})
         out["dt"] = np.array(dt)
-        np.savez_compressed(os.path.join(HERE, "pvfilter.npz"), **out)
+        golden_io.save(os.path.join(HERE, "pvfilter.npz"), **out)   # in parts once it passes 1 MB
     finally:
         torch.set_default_dtype(torch.float32)
 
@@ -361,7 +364,7 @@ def gen_learner(ref):
         out["actor." + k] = t.numpy()
     for k, t in critic.state_dict().items():
         out["critic." + k] = t.numpy()
-    np.savez_compressed(os.path.join(HERE, "learner.npz"), **out)
+    golden_io.save(os.path.join(HERE, "learner.npz"), **out)   # in parts: each file under 1 MB
 
 
 if __name__ == "__main__":

@@ -176,3 +176,49 @@ def test_headline_prices_the_driver_launch(monkeypatch):
     assert abs(e["bytes_per_env_step"] - B.rollout_bytes_per_env_step("LeeLanded", 20)) < 0.01
     assert e["traffic"] == td["bytes_per_launch"] and abs(e["traffic_alg_ratio"] - e["traffic"] / (
         B.rollout_bytes_per_env_step("LeeLanded", 20) * 4096 * 20)) <= 1e-3
+
+
+def _fake_outputs(n, k):
+    import torch
+    g = torch.Generator().manual_seed(0)
+    st = (torch.rand((k, n, 13), generator=g), torch.rand((k, n), generator=g),
+          torch.randint(0, 2, (k, n), generator=g), torch.rand((k, n), generator=g) > 0.5)
+    out = {}
+    for name, t in zip(("obs", "rew", "reset", "time_outs"), st):
+        out["rollout_" + name] = t
+        out[name] = t[k - 1]
+    out["episode_stats"] = torch.tensor([1.5, 2.0, 30.0], dtype=torch.float64)
+    return out
+
+
+def test_dump_outputs_writes_float_arrays_and_samples_large_ones(tmp_path, monkeypatch):
+    """``--dump-outputs``: one .npy per output, float32 (float64 statistics), values unchanged; a set above the
+    size limit is cut to a fixed, seeded sample of envs that is the same from call to call and fits the limit."""
+    import numpy as np
+    n, k = 700, 3
+    outs = _fake_outputs(n, k)
+    B.write_outputs(str(tmp_path / "a"), outs, n)
+    assert sorted(os.listdir(tmp_path / "a")) == sorted(name + ".npy" for name in outs)
+    for name, t in outs.items():
+        a = np.load(tmp_path / "a" / (name + ".npy"))
+        assert a.dtype == (np.float64 if name == "episode_stats" else np.float32) and a.shape == tuple(t.shape)
+        assert np.array_equal(a, t.numpy().astype(a.dtype))
+    monkeypatch.setattr(B, "DUMP_LIMIT_BYTES", (1 << 20) + 40000)
+    for d in ("b", "c"):
+        B.write_outputs(str(tmp_path / d), outs, n)
+    idx = np.load(tmp_path / "b" / "env_index.npy")
+    assert np.array_equal(idx, np.load(tmp_path / "c" / "env_index.npy"))
+    idx = idx.astype(np.int64)
+    assert 0 < len(idx) < n and np.all(np.diff(idx) > 0) and idx[-1] < n
+    assert np.array_equal(np.load(tmp_path / "b" / "rollout_obs.npy"), outs["rollout_obs"].numpy()[:, idx])
+    assert np.array_equal(np.load(tmp_path / "b" / "rew.npy"), outs["rew"].numpy()[idx])
+    assert sum(os.path.getsize(tmp_path / "b" / f) for f in os.listdir(tmp_path / "b")) <= (1 << 20) + 40000
+
+
+def test_plain_run_is_the_default_and_full_is_an_option(monkeypatch):
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = B.parse()
+    assert not a.full and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = B.parse()
+    assert a.full and a.dump_outputs == "d"

@@ -72,3 +72,53 @@ def test_bench_spawns_its_ranks():
     assert d["n_gpus"] == 2 and d["config"]["global_envs"] == 8192 and d["config"]["ranks_joined"] == 2
     assert d["config"]["launcher"] == "bench.py" and d["config"]["backend"] == "gloo"
     assert d["split_timeouts"] == 0 and d["value"] > 0
+
+
+def test_plain_bench_times_the_headline_only_and_dumps_its_outputs(tmp_path):
+    """A plain ``bench.py --gpus 1 --steps N --warmup W``: the headline fields, none of the ``--full`` legs, no
+    side file; ``--dump-outputs`` holds the last timed launch's storage rows (N = 40: launches of 32 + 8)."""
+    import numpy as np
+    if not torch.cuda.is_available():
+        pytest.skip("needs a HIP device")
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    def bench(out):
+        return subprocess.run([sys.executable, "-u", os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "40",
+                               "--warmup", "5", "--num-envs", "1000", "--dump-outputs", str(tmp_path / out)],
+                              env=env, capture_output=True, text=True, timeout=120, cwd=str(tmp_path))
+    p = bench("out")
+    assert p.returncode == 0, (p.stdout + p.stderr)[-3000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, p.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["steps"] == 40 and d["config"]["launches"] == [32, 8] and d["unit"] == "env-steps/s"
+    assert d["higher_is_better"] is True and d["dtype"] == "f32" and d["split_timeouts"] == 0
+    assert d["ms_per_step"] > 0 and abs(d["value"] - 1000 / (d["ms_per_step"] * 1e-3)) <= 0.02 * d["value"]
+    for k in ("per_step_launch", "configs", "large_n", "cpu_baseline"):
+        assert k not in d, k
+    assert d["detail"] is None and os.listdir(tmp_path) == ["out"]
+    obs = np.load(tmp_path / "out" / "rollout_obs.npy")
+    assert obs.dtype == np.float32 and obs.shape == (8, 1000, 13) and np.isfinite(obs).all()
+    assert np.array_equal(np.load(tmp_path / "out" / "obs.npy"), obs[-1])
+    assert np.load(tmp_path / "out" / "rew.npy").shape == (1000,)
+    assert np.load(tmp_path / "out" / "episode_stats.npy").dtype == np.float64
+    # the same arguments give the same inputs, so a second run's outputs are equal bit for bit
+    p2 = bench("again")
+    assert p2.returncode == 0, (p2.stdout + p2.stderr)[-3000:]
+    names = sorted(os.listdir(tmp_path / "out"))
+    assert names == sorted(os.listdir(tmp_path / "again")) and len(names) == 9
+    for f in names:
+        assert np.array_equal(np.load(tmp_path / "out" / f), np.load(tmp_path / "again" / f)), f
+    # and they are what a caller of the env gets from the same launches (5 warm-up steps, then 32 + 8) with the
+    # bench's seed: the same kernel on the same state, so equal bit for bit (LeeLanded ignores its actions)
+    from ouzelum_amd import QuadVecTask
+    envq = QuadVecTask(task="LeeLanded", num_envs=1000, sim_device="cuda:0", rl_device="cuda:0", seed=1234,
+                       env_id_offset=0, num_envs_total=1000, track_episodes=True)
+    st = _storage(1000, 32)
+    stats = torch.zeros(3, dtype=torch.float64, device="cuda:0")
+    for k in (5, 32, 8):
+        envq.rollout(None, k, fused=True, storage=tuple(t[:k] for t in st), stats_out=stats, check=True)
+    torch.cuda.synchronize()
+    assert np.array_equal(obs, st[0][:8].cpu().numpy())
+    assert np.array_equal(np.load(tmp_path / "out" / "rollout_rew.npy"), st[1][:8].cpu().numpy())
+    assert np.array_equal(np.load(tmp_path / "out" / "rollout_reset.npy"), st[2][:8].cpu().numpy().astype(np.float32))
+    assert np.array_equal(np.load(tmp_path / "out" / "episode_stats.npy"), stats.cpu().numpy())

@@ -133,3 +133,26 @@ def test_reward_matches_reference(golden, task, z_die):
     rew, reset = Q.compute_reward(p, tgt, q, w, None, g["progress"], int(g[f"{task}_max_ep"]), z_die)
     np.testing.assert_allclose(rew, g[f"{task}_rew"], rtol=2e-6, atol=2e-6)
     np.testing.assert_array_equal(reset, g[f"{task}_reset"])
+
+
+def test_fixture_parts_round_trip_and_stay_under_the_file_limit(tmp_path, monkeypatch):
+    """tests/golden_io.py: a set of arrays saved in parts comes back whole, in order and bit for bit; every
+    committed fixture file is below the limit for one file."""
+    import glob
+    import os
+    from tests import golden_io as G
+    rng = np.random.default_rng(0)
+    arrays = {f"a{i}": rng.standard_normal((40, 50 + i)) for i in range(6)}
+    arrays["flag"] = np.array(3)
+    monkeypatch.setattr(G, "PART_LIMIT", 40000)
+    p = str(tmp_path / "set.npz")
+    G.save(p, **arrays)
+    assert len(G.parts(p)) > 2 and all(os.path.getsize(q) <= 40000 for q in G.parts(p))
+    back = G.load(p)
+    assert back.files == list(arrays)
+    for k, a in arrays.items():
+        assert back[k].dtype == a.dtype and back[k].shape == a.shape and back[k].tobytes() == a.tobytes()
+    G.save(p, flag=np.array(4))   # a shorter set leaves no stale parts behind
+    assert G.parts(p) == [p] and int(G.load(p)["flag"]) == 4
+    here = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+    assert all(os.path.getsize(f) <= (1 << 20) for f in glob.glob(os.path.join(here, "*")) if os.path.isfile(f))

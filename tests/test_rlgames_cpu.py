@@ -48,6 +48,24 @@ def test_reference_task_yamls(task, max_ep):
         assert kw["max_episode_length"] == max_ep
 
 
+@pytest.mark.parametrize("pomdp_keys", [True, False])
+def test_task_yaml_file_is_parsed_and_resolved(tmp_path, pomdp_keys):
+    """``load_task_yaml`` on a file this test writes itself (INLINE as YAML, with and without the POMDP keys): the
+    file path of the adapter without anything outside the repository.  Not a stand-in for the reference's own
+    files, which ``test_reference_task_yamls`` reads where they are present."""
+    import yaml
+    env = {k: v for k, v in INLINE["env"].items() if pomdp_keys or k not in ("POMDP", "pomdp_prob")}
+    path = tmp_path / "task.yaml"
+    with open(path, "w") as fh:
+        yaml.safe_dump({**INLINE, "env": env}, fh)
+    kw = R.env_kwargs_from_task_config(R.load_task_yaml(str(path), num_envs=512))
+    assert kw == {"task": "EKFLeeLanded", "num_envs": 512, "max_episode_length": 700, "convergence_time": 300,
+                  "dt": 0.01, "substeps": 2}
+    if pomdp_keys:
+        kw = R.env_kwargs_from_task_config(R.load_task_yaml(str(path), POMDP="random_noise", pomdp_prob=0.15))
+        assert kw["num_envs"] == 4096 and kw["pomdp"] == "random_noise" and kw["pomdp_prob"] == 0.15
+
+
 def test_registration_and_env_info_shape():
     made = []
 
