@@ -385,8 +385,9 @@ def waypoint_tables():
 # ---------------------------------------------------------------------------
 # Reward / observation (a16, a17)
 # ---------------------------------------------------------------------------
-def compute_reward(p, target, q, w, reset_buf, progress, max_episode_length, z_die):
-    """compute_ingenuity_reward (tasks/ekf_lee_landed.py:692-723; ouzelum.py:302-332)."""
+def compute_reward(p, target, q, w, reset_buf, progress, max_episode_length, z_die, bias=0.0):
+    """compute_ingenuity_reward (tasks/ekf_lee_landed.py:692-723; ouzelum.py:302-332).  ``bias`` is added to the
+    compared quantity of both die lines (OracleEnv.decision_bias), not to the reward's distance."""
     d = np.sqrt(((target - p) ** 2).sum(-1))
     pos_r = 1.0 / (1.0 + d * d)
     ups = quat_axis_z(q)
@@ -395,8 +396,8 @@ def compute_reward(p, target, q, w, reset_buf, progress, max_episode_length, z_d
     spin = np.abs(w[..., 2])
     spin_r = 1.0 / (1.0 + spin * spin)
     rew = pos_r + pos_r * (up_r + spin_r)
-    die = np.where(d > 8.0, 1, 0)
-    die = np.where(p[..., 2] < z_die, 1, die)
+    die = np.where(d + bias > 8.0, 1, 0)
+    die = np.where(p[..., 2] + bias < z_die, 1, die)
     reset = np.where(progress >= max_episode_length - 1, 1, die)
     return rew, reset.astype(np.int64)
 
@@ -433,12 +434,13 @@ def map_to_pi(a):
     return np.where(a <= -math.pi, a + 2 * math.pi, a)
 
 
-def drive_command(cur, tgt, heading, gains=(DRIVE_GAIN_LIN, DRIVE_GAIN_ANG), max_wheel=MAX_WHEEL_SPEED):
+def drive_command(cur, tgt, heading, gains=(DRIVE_GAIN_LIN, DRIVE_GAIN_ANG), max_wheel=MAX_WHEEL_SPEED, bias=0.0):
     """differential_drive (utils/controllers.py:15-43) -> saturated (linear, angular) velocity and the
-    wheel speeds (right, left, right, left) it returns."""
+    wheel speeds (right, left, right, left) it returns.  ``bias`` is added to |dth| before the dead-band
+    comparison (OracleEnv.decision_bias)."""
     dx, dy = tgt[:, 0] - cur[:, 0], tgt[:, 1] - cur[:, 1]
     dth = map_to_pi(np.arctan2(dy, dx) - map_to_pi(heading))
-    dth = np.where((dth < DRIVE_ANG_THRESH) & (dth > -DRIVE_ANG_THRESH), 0.0, dth)
+    dth = np.where((dth + bias < DRIVE_ANG_THRESH) & (dth - bias > -DRIVE_ANG_THRESH), 0.0, dth)
     lin = np.sqrt(dx ** 2 + dy ** 2) * gains[0]
     ang = dth * gains[1]
     left = (2 * lin + ang * WHEEL_BASE) / (2 * WHEEL_RADIUS)
@@ -449,11 +451,24 @@ def drive_command(cur, tgt, heading, gains=(DRIVE_GAIN_LIN, DRIVE_GAIN_ANG), max
     return lin * sc, ang * sc, wheels
 
 
-def deck_contact(p, v, w, on, plat, plat_v):
+def deck_contact(p, v, w, on, plat, plat_v, bias=0.0, offsets=None, hits=None):
     """Inelastic sticking contact with the deck: a drone inside the footprint and below the rest
-    height is put on the deck, moves with the platform, and stops rotating."""
+    height is put on the deck, moves with the platform, and stops rotating.  ``bias`` is added to r^2 and to
+    p.z before they are compared (OracleEnv.decision_bias); ``offsets``: a dict whose "deck_r" / "deck_z"
+    entries take this call's signed distances from the two lines where they are nearer than the recorded ones
+    (each where the other condition holds within the bias band, so that it is this line that decides);
+    ``hits``: a bool array, set where the contact fired."""
     dxy = p[:, 0:2] - plat
-    hit = on & ((dxy ** 2).sum(-1) < DECK_RADIUS ** 2) & (p[:, 2] < DECK_Z_REST)
+    r2 = (dxy ** 2).sum(-1)
+    hit = on & (r2 + bias < DECK_RADIUS ** 2) & (p[:, 2] + bias < DECK_Z_REST)
+    if hits is not None:
+        hits |= hit
+    if offsets is not None:
+        band = 4e-4
+        for key, val, other in (("deck_z", p[:, 2] - DECK_Z_REST, r2 < DECK_RADIUS ** 2 + band),
+                                ("deck_r", r2 - DECK_RADIUS ** 2, p[:, 2] < DECK_Z_REST + band)):
+            val = np.where(on & other, val, np.inf)
+            offsets[key] = np.where(np.abs(val) < np.abs(offsets[key]), val, offsets[key])
     if hit.any():
         p, v, w = p.copy(), v.copy(), w.copy()
         p[hit, 2] = DECK_Z_REST
@@ -464,7 +479,7 @@ def deck_contact(p, v, w, on, plat, plat_v):
 
 
 def integrate(p, q, v, w, f_b, tau_b, mass, inertia, dt=DT, substeps=SUBSTEPS, wmax=MAX_ANGVEL, contact=None,
-              gravity=None):
+              gravity=None, contact_bias=0.0, offsets=None, hits=None):
     """Semi-implicit Euler over ``substeps`` sub-steps on a lumped rigid body.
 
     f_b, tau_b: body-frame force (N) and torque (N m) at the COM (LOCAL_SPACE,
@@ -489,7 +504,7 @@ def integrate(p, q, v, w, f_b, tau_b, mass, inertia, dt=DT, substeps=SUBSTEPS, w
         w = w * scale[:, None]
         p = p + h * v
         if contact is not None:          # (on mask, platform xy, platform velocity xy)
-            p, v, w = deck_contact(p, v, w, *contact)
+            p, v, w = deck_contact(p, v, w, *contact, bias=contact_bias, offsets=offsets, hits=hits)
         n = np.linalg.norm(w, axis=-1)
         th = 0.5 * h * n
         s = np.where(th < 1e-4, 0.5 * h * (1.0 - th * th / 6.0), np.sin(th) / np.maximum(n, 1e-30))
@@ -814,6 +829,15 @@ class OracleEnv:
         self.land_flag = np.zeros(n, np.int64)
         self.landings = np.zeros(n, np.int64)
         self.tables = waypoint_tables()
+        # Test instrumentation of the step's real-valued discrete decisions.  decision_bias is added to the compared
+        # quantity of each of them (hover / landing cut, waypoint re-aim and final approach, both die lines, deck
+        # height and radius, husky waypoint switch and |dth| of its dead band) before the comparison; 0.0 changes
+        # nothing.  margins[name] (n,): how far the last step's compared quantity was from that line (inf where the
+        # env did not evaluate it); offsets[name]: the same, signed (compared quantity - line).
+        self.decision_bias = 0.0
+        self.offsets = self._no_offsets()
+        self.deck_hit = np.zeros(n, bool)
+        self.plat_margin = None
         for t, s in self.specs.items():
             m = self.task_ids == t
             if s.target_mode in (TGT_PLATFORM, TGT_TRAJ):
@@ -822,6 +846,38 @@ class OracleEnv:
                 self.target[m, 2] = 1.0              # ouzelum.py:73
             if s.target_mode == TGT_TRAJ:
                 self._new_traj(m, rng.INIT_STEP)
+
+    MARGIN_NAMES = ("hover", "land", "reaim_lo", "reaim_hi", "final", "die_far", "die_z", "deck_z", "deck_r",
+                    "husky_switch", "husky_band", "husky_wrap")
+
+    def _no_offsets(self):
+        return {k: np.full(self.n, np.inf) for k in self.MARGIN_NAMES}
+
+    @property
+    def margins(self):
+        return {k: np.abs(v) for k, v in self.offsets.items()}
+
+    def min_margin(self):
+        """Per env: the last step's distance from the nearest of its real-valued decision lines."""
+        return np.minimum.reduce([np.abs(self.offsets[k]) for k in self.MARGIN_NAMES])
+
+    def take(self, idx):
+        """A new OracleEnv over the envs ``idx`` (any order) of this one: same config, step counter and job size,
+        ``gid`` / ``task_ids`` and every per-env array sliced (copies).  Every draw and the shared PV trigger
+        counter are keyed on ``gid``, so stepping it gives bitwise the rows ``idx`` of stepping this env."""
+        idx = np.asarray(idx, np.int64).reshape(-1)
+        new = object.__new__(OracleEnv)
+        for k, val in self.__dict__.items():
+            if isinstance(val, np.ndarray) and val.ndim >= 1 and val.shape[0] == self.n and k != "tables":
+                new.__dict__[k] = val[idx].copy()
+            else:
+                new.__dict__[k] = val
+        new.n = len(idx)
+        new.cfg = replace(self.cfg, num_envs=new.n)
+        new.n_total = self.n_total
+        new.specs = {t: s for t, s in self.specs.items() if np.any(new.task_ids == t)}
+        new.offsets = {k: v[idx].copy() for k, v in self.offsets.items()}
+        return new
 
     # -- draws ---------------------------------------------------------------
     def _new_traj(self, m, step):
@@ -858,6 +914,9 @@ class OracleEnv:
         ids = self.gid
         f_b = np.zeros((n, 3), dtype)
         tau_b = np.zeros((n, 3), dtype)
+        bias = self.decision_bias
+        self.offsets = self._no_offsets()
+        self.deck_hit = np.zeros(n, bool)      # the deck contact fired in a sub-step of this step
 
         # ---- lazy reset (ekf_lee_landed.py:312-335; ouzelum.py:221-233) ----
         wr = rng.draw_u32(cfg.seed, ids, t, rng.RNG_RESET_POS)
@@ -918,7 +977,8 @@ class OracleEnv:
         grav = gravity_dr(cfg.dr_gravity, cfg.seed, t) if cfg.dr_gravity and cfg.dr_gravity["distribution"] else None
         self.p, self.q, self.v, self.w = integrate(self.p, self.q, self.v, self.w, f_b, tau_b,
                                                    mass.astype(dtype), inertia.astype(dtype), dt, cfg.substeps,
-                                                   contact=(deck_on, self.plat, self.plat_v), gravity=grav)
+                                                   contact=(deck_on, self.plat, self.plat_v), gravity=grav,
+                                                   contact_bias=bias, offsets=self.offsets, hits=self.deck_hit)
 
         # ---- post_physics_step (ekf_lee_landed.py:620-685) ----
         self.progress += 1
@@ -935,7 +995,9 @@ class OracleEnv:
             m = self.task_ids == task
             obs[m] = pomdp_apply(obs[m], spec.pomdp, spec.pomdp_prob, cfg.seed, ids[m], t, rng.SITE_OBS, task)
             r, rs = compute_reward(self.p[m], self.target[m], self.q[m], self.w[m], self.reset_buf[m],
-                                   self.progress[m], spec.max_episode_length, spec.z_die)
+                                   self.progress[m], spec.max_episode_length, spec.z_die, bias)
+            self.offsets["die_far"][m] = np.sqrt(((self.target[m] - self.p[m]) ** 2).sum(-1)) - 8.0
+            self.offsets["die_z"][m] = self.p[m, 2] - spec.z_die
             rew[m] = r
             reset[m] = rs
             maxlen[m] = spec.max_episode_length
@@ -988,7 +1050,8 @@ class OracleEnv:
         T, tau = lee_position(state, cmd)
         fz = 2 * GRAVITY * T
         dist = np.sqrt(((cmd[:, 0:3] - state[:, 0:3]) ** 2).sum(-1))
-        cut = dist < spec.land_radius
+        cut = dist + self.decision_bias < spec.land_radius
+        self.offsets["hover"][m] = dist - spec.land_radius
         self.land_flag[np.nonzero(m)[0][cut]] = 1
         fz = np.where(cut, 0.0, fz)
         tau = np.where(cut[:, None], 0.0, tau)
@@ -1049,13 +1112,18 @@ class OracleEnv:
             wp = target.copy()                                  # :464-466
         td = np.sqrt(((target - p) ** 2).sum(-1))
         wd = np.sqrt(((wp - p) ** 2).sum(-1))
+        bias = self.decision_bias
         if not conv:                                            # :476-490
-            chk = (wd < 0.5) | (wd > 1.0)
+            self.offsets["reaim_lo"][m] = wd - 0.5
+            self.offsets["reaim_hi"][m] = wd - 1.0
+            self.offsets["final"][m] = td - 0.75
+            self.offsets["land"][m] = td - spec.land_radius
+            chk = (wd + bias < 0.5) | (wd + bias > 1.0)
             raised = target + np.array([0, 0, 0.7])
             vec = raised - p
             nv = vec / np.sqrt((vec ** 2).sum(-1, keepdims=True)) * 0.75 + p
             wp = np.where(chk[:, None], nv, wp)
-            chk2 = td < 0.75
+            chk2 = td + bias < 0.75
             wp = np.where(chk2[:, None], target + np.array([0, 0, 0.09]), wp)
         cmd = np.concatenate([wp, np.zeros((wp.shape[0], 1))], 1)
         if conv:
@@ -1064,7 +1132,7 @@ class OracleEnv:
             st = np.concatenate([pv_x[:, 0:3], q, pv_x[:, 3:6], w], 1)  # :497-500
         T, tau = lee_position(st, cmd)
         fz = 2 * GRAVITY * T                                    # :458,504
-        cut = td < spec.land_radius                             # :508-515
+        cut = td + bias < spec.land_radius                      # :508-515
         if not conv:
             idx = np.nonzero(m)[0][cut]
             self.land_flag[idx] = 1
@@ -1093,15 +1161,23 @@ class OracleEnv:
         wp = self._traj_point(self.traj_idx)
         d = np.sqrt(((wp - self.plat) ** 2).sum(-1))
         margin = np.abs(d - 0.2)                 # distance of this step's decisions from their thresholds
-        adv = m & (d < 0.2)
+        self.offsets["husky_switch"] = np.where(m, d - 0.2, self.offsets["husky_switch"])
+        adv = m & (d + self.decision_bias < 0.2)
         self.traj_idx[adv] += 1
         done = m & (self.traj_idx >= self._traj_len())
         if done.any():
             self._new_traj(done, t)
         wp = self._traj_point(self.traj_idx)
-        lin, ang, _ = drive_command(self.plat, wp, self.plat_heading, max_wheel=cfg.plat_speed / WHEEL_RADIUS)
-        dth = map_to_pi(np.arctan2(wp[:, 1] - self.plat[:, 1], wp[:, 0] - self.plat[:, 0]) - map_to_pi(self.plat_heading))
-        margin = np.minimum(margin, np.abs(np.abs(dth) - DRIVE_ANG_THRESH))
+        lin, ang, _ = drive_command(self.plat, wp, self.plat_heading, max_wheel=cfg.plat_speed / WHEEL_RADIUS,
+                                    bias=self.decision_bias)
+        raw = np.arctan2(wp[:, 1] - self.plat[:, 1], wp[:, 0] - self.plat[:, 0]) - map_to_pi(self.plat_heading)
+        dth = map_to_pi(raw)
+        # the wrap of the heading error (utils/controllers.py:5-13): a jump of 2 pi at raw = pi / -pi; takes no bias
+        wrap = np.where(np.abs(raw - math.pi) < np.abs(raw + math.pi), raw - math.pi, raw + math.pi)
+        self.offsets["husky_wrap"] = np.where(m, wrap, self.offsets["husky_wrap"])
+        band = np.abs(dth) - DRIVE_ANG_THRESH
+        self.offsets["husky_band"] = np.where(m, band, self.offsets["husky_band"])
+        margin = np.minimum(margin, np.abs(band))
         self.plat_margin = np.where(m, margin, np.inf) if getattr(self, "plat_margin", None) is None \
             else np.where(m, margin, self.plat_margin)
         th = map_to_pi(self.plat_heading + ang * cfg.dt)

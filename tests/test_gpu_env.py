@@ -11,11 +11,16 @@ import pytest
 import torch
 
 from oracle import quad_oracle as Q
+from tests.decision_cases import assert_excluded_match_a_branch
 from tests.hip_helpers import gpu_snapshot, gpu_to_oracle, oracle_snapshot, quat_canon
 
 pytestmark = pytest.mark.gpu
 
 TASKS = ["Ouzelum", "LeeLanded", "EKFLeeLanded", "QuadTracking", "QuadFault", "QuadMixed", "Landing"]
+# what the single-step tests compare on the envs away from every done line; the envs near one are compared in the same
+# fields with either branch of the oracle (decision_cases.assert_excluded_match_a_branch)
+PARITY_FIELDS = ("p", "v", "w", "q", "obs", "rew", "target", "reset", "timeouts", "progress", "land_flag")
+DECK_FIELDS = ("p", "v", "w", "obs", "rew", "reset")
 
 
 @pytest.fixture(scope="module")
@@ -78,12 +83,15 @@ def test_single_step_parity(ouz, task, off, n):
         a = actions_for(rs, n)
         if k >= 15 and k % 3 == 0:          # compare at several points, before and after the EKF warm-up
             gpu_to_oracle(env, o)
+            pre = o.take(np.arange(n))
             o.step(a)
             env.step(torch.as_tensor(a, device="cuda"))
             g = gpu_snapshot(env)
             r = oracle_snapshot(o)
             tie = near_threshold(o)
             ok = ~tie
+            # the envs left out below must still be one of the two branches of the line they are near
+            assert_excluded_match_a_branch(f"{task}@{k}", g, pre, tie, a, PARITY_FIELDS)
             assert_close(f"{task}@{k} p", g["p"][ok], r["p"][ok], 2e-5, 2e-5)
             assert_close(f"{task}@{k} v", g["v"][ok], r["v"][ok], 1e-4, 1e-5)
             assert_close(f"{task}@{k} w", g["w"][ok], r["w"][ok], 1e-3, 1e-4)
@@ -119,10 +127,12 @@ def test_single_step_parity_on_the_deck(ouz, task):
         env.step(None)
     for k in range(3):
         gpu_to_oracle(env, o)
+        pre = o.take(np.arange(n))
         o.step(np.zeros((n, 4)))
         env.step(None)
         g, r = gpu_snapshot(env), oracle_snapshot(o)
         ok = ~near_threshold(o)
+        assert_excluded_match_a_branch(f"{task} deck", g, pre, ~ok, np.zeros((n, 4)), DECK_FIELDS)
         on_deck = np.abs(r["p"][:, 2] - Q.DECK_Z_REST) < 1e-9
         if task != "LeeLanded":
             assert on_deck.sum() > n // 4, f"only {on_deck.sum()} drones on the deck"

@@ -13,10 +13,12 @@ import torch
 
 import ouzelum_amd
 from oracle import quad_oracle as Q
+from tests.decision_cases import assert_excluded_match_a_branch
 from tests.hip_helpers import gpu_snapshot, gpu_to_oracle, oracle_snapshot, quat_canon
 
 TASKS = ["Ouzelum", "LeeLanded", "EKFLeeLanded", "QuadTracking", "QuadFault", "QuadMixed", "Landing"]
 ESTIMATOR = ("EKFLeeLanded", "QuadTracking", "QuadMixed")
+PARITY_FIELDS = ("p", "v", "w", "q", "obs", "rew", "target", "reset", "timeouts", "progress", "land_flag")
 
 
 def make_pair(task, n, seed=0, **kw):
@@ -63,10 +65,13 @@ def test_host_single_step_parity(task, off, n):
         a = rs.uniform(-1.0, 1.0, (n, 4)).astype(np.float32)
         if k >= 15 and k % 6 == 0:
             gpu_to_oracle(env, o)
+            pre = o.take(np.arange(n))
             o.step(a)
             env.step(torch.as_tensor(a))
             g, r = gpu_snapshot(env), oracle_snapshot(o)
             ok = ~near_threshold(o)
+            # the envs left out below must still be one of the two branches of the line they are near
+            assert_excluded_match_a_branch(f"{task}@{k}", g, pre, ~ok, a, PARITY_FIELDS)
             assert_close(f"{task}@{k} p", g["p"][ok], r["p"][ok], 2e-5, 2e-5)
             assert_close(f"{task}@{k} v", g["v"][ok], r["v"][ok], 1e-4, 1e-5)
             assert_close(f"{task}@{k} w", g["w"][ok], r["w"][ok], 1e-3, 1e-4)
