@@ -196,6 +196,7 @@ struct StepArgs {
   int32_t outw;                // latency-regime rollouts with an output wave (OUZ_OUT_WAVE; out_wave)
   int32_t xcd_pack;            // class layout above the latency regime: a class block's waves on one XCD (xcd_tile)
   int32_t mix_split;           // mixed curriculum above the latency regime: one launch per task (mixed_task_tile)
+  int32_t plain;               // output-wave rollouts: the plain-config kernels where a launch allows (OUZ_PLAIN_ROLLOUT)
   const ouz_dr_noise* drn;    // VecTask DR noise params in device memory: [0] observations, [1] actions
   int32_t drn_mask;            // bit 0: observation noise on, bit 1: action noise on
   float* trace;                // ouz_set_trace: [trace_cap][9] (p, target, v) of env trace_env
@@ -544,7 +545,8 @@ OUZ_DEV void load_actions(const float* actions, EnvRegs<CTRL, TGT>& S, int e = 0
 }
 
 // QLN: the quad-lane estimator (quad_pv_ql.h): the PV covariance goes to LDS (pv_lds_load), not to registers.
-template <int CTRL, int TGT, bool CLS = false, bool NTL = false, bool QLN = false>
+// PLAIN: a plain-config launch (plain_config): no physical DR, the scales are the constant 1.
+template <int CTRL, int TGT, bool CLS = false, bool NTL = false, bool QLN = false, bool PLAIN = false>
 OUZ_DEV void env_load(const StepArgs& a, int i, const TaskParams& tp, EnvRegs<CTRL, TGT>& S,
                                          const float* actions) {
   // reset_buf and time_outs are read unconditionally and combined without a branch, so the two flag
@@ -574,7 +576,7 @@ OUZ_DEV void env_load(const StepArgs& a, int i, const TaskParams& tp, EnvRegs<CT
   S.ep_sum_add = 0.0f;
   S.ep_ret = a.track_episodes ? L(OUZ_F_EP_RET) : 0.0f;
   S.dr_m = S.dr_i = S.dr_t = 1.0f;
-  if (tp.dr) { S.dr_m = L(OUZ_F_DR); S.dr_i = L(OUZ_F_DR + 1); S.dr_t = L(OUZ_F_DR + 2); }
+  if (!PLAIN && tp.dr) { S.dr_m = L(OUZ_F_DR); S.dr_i = L(OUZ_F_DR + 1); S.dr_t = L(OUZ_F_DR + 2); }
   if constexpr (TGT == TGT_GOAL) S.target = L3(OUZ_F_TARGET);
   if constexpr (CTRL == CTRL_RL) {
 #pragma unroll
@@ -716,6 +718,7 @@ OUZ_DEV void platform_step(const StepArgs& a, const StepCtx& sc, uint32_t gid,
 
 // compute_observations + compute_ingenuity_reward of the post-step state (ekf_lee_landed.py:653-723,
 // vec_task.py:351-353): one body for the one-wave step and the output wave (out_wave).
+template <bool PLAIN = false>
 OUZ_DEV void obs_reward(const StepArgs& a, const StepCtx& sc, const TaskParams& tp, int task,
                                            uint32_t gid, V3 p, Q4 q, V3 v, V3 w, V3 target, float* ob, float& rew,
                                            float& dist) {
@@ -724,7 +727,7 @@ OUZ_DEV void obs_reward(const StepArgs& a, const StepCtx& sc, const TaskParams& 
   ob[7] = v.x * 0.5f; ob[8] = v.y * 0.5f; ob[9] = v.z * 0.5f;
   ob[10] = w.x / kPiF; ob[11] = w.y / kPiF; ob[12] = w.z / kPiF;
   pomdp_apply<13>(ob, tp, task, a, sc, gid, SITE_OBS, false);
-  if (a.drn_mask & 1) dr_noise_apply<13>(ob, a.drn[0], a.seed, gid, sc.step, RNG_DRN_OBS);   // vec_task.py:351-352
+  if (!PLAIN && (a.drn_mask & 1)) dr_noise_apply<13>(ob, a.drn[0], a.seed, gid, sc.step, RNG_DRN_OBS);   // vec_task.py:351-352
 #pragma unroll
   for (int k = 0; k < 13; ++k) ob[k] = fminf(fmaxf(ob[k], -5.0f), 5.0f);   // vec_task.py:353
   rew = reward(p, target, q, w, dist);
@@ -740,14 +743,24 @@ OUZ_DEV void obs_reward(const StepArgs& a, const StepCtx& sc, const TaskParams& 
 // OWV: a rollout with an output wave: the step stops at the done decision; the output wave forms the
 // observation, reward and episode statistics from the post-step state (out_wave), so `ob` / `rew` are not
 // written here and the step's target goes to *post_target.
-template <int CTRL, int TGT, bool PRE = false, bool QLN = false, bool SPW = false, bool OWV = false>
+// PLAIN: a plain-config launch (plain_config): what that predicate fixes is a constant here instead of a load, a
+// select or a branch on StepArgs; the arithmetic of the path that remains is the general form's, operation for
+// operation (a scale that is the constant 1 multiplies exactly).
+// CARRY: *Rc holds quat_to_mat(S.q) on entry (the fused rollout's previous step formed it for the world-frame body
+// rate, run_env before the first step) and of the post-step quaternion on return: the same function of the same
+// quaternion as forming it here, without the second evaluation on the step's dependent chain.
+template <int CTRL, int TGT, bool PRE = false, bool QLN = false, bool SPW = false, bool OWV = false,
+          bool PLAIN = false, bool CARRY = false>
 OUZ_DEV void env_core(const StepArgs& a, const StepCtx& sc, int i, uint32_t gid, int task,
                                          EnvRegs<CTRL, TGT>& S, float* ob, float& rew, bool& rs, bool& timeout,
                                          float* wrench = nullptr, const PvQl* ql = nullptr,
-                                         const SplitLane* spl = nullptr, V3* post_target = nullptr) {
+                                         const SplitLane* spl = nullptr, V3* post_target = nullptr, M3* Rc = nullptr) {
+  static_assert(!CARRY || (!PRE && CTRL != CTRL_LEE_EST), "R(q) is carried by the rollouts of the tasks without the estimator");
   const TaskParams& tp = a.tp[tp_slot(task)];
   const EnvConsts& c = a.c;
   const bool rst = S.rst;
+  const bool dr = !PLAIN && tp.dr;                       // physical DR of the task
+  const int32_t drn_mask = PLAIN ? 0 : a.drn_mask;       // observation / action noise, gravity DR
   // target_root_positions: random goals are state (ouzelum.py:180-190); a platform target is
   // platform xy + offset at z 0.377 (ekf_lee_landed.py:87,628-629), recomputed rather than stored.
   // Before the first post_physics_step it is still (0, 0, 0.377).
@@ -760,12 +773,13 @@ OUZ_DEV void env_core(const StepArgs& a, const StepCtx& sc, int i, uint32_t gid,
     U4 r = draw(a.seed, gid, sc.step, RNG_RESET_POS);
     S.p = v3(uniform_f32(r.x, -1.5f, 1.5f), uniform_f32(r.y, -1.5f, 1.5f), __fadd_rn(1.0f, uniform_f32(r.z, -0.2f, 1.5f)));
     S.q = Q4{0.0f, 0.0f, 0.0f, 1.0f};
+    if constexpr (CARRY) *Rc = quat_to_mat(S.q);
     S.v = v3(0.0f, 0.0f, 0.0f);
     S.w = v3(0.0f, 0.0f, 0.0f);
     S.progress = 0;
     if (S.land_flag < 0) S.land_flag = ldi(S.T, OUZ_I_LAND_FLAG);   // landing counter (ekf_lee_landed.py:323-331)
     if (S.land_flag) { S.landings_add += S.land_flag; S.land_flag = 0; S.dirty |= D_LAND; }
-    if (tp.dr) {
+    if (dr) {
       // VecTask.apply_randomizations at reset (vec_task.py:547-563): the envs in the reset buffer whose
       // randomize_buf = step - OUZ_I_RAND_STEP >= frequency, and every env on its first randomization.  With
       // frequency <= 1 and no setup_only parameter every reset is due (an env resets at most once per step), so
@@ -814,7 +828,7 @@ OUZ_DEV void env_core(const StepArgs& a, const StepCtx& sc, int i, uint32_t gid,
       }
     }
     float av[4] = {S.act.x, S.act.y, S.act.z, S.act.w};
-    if (a.drn_mask & 2) dr_noise_apply<4>(av, a.drn[1], a.seed, gid, sc.step, RNG_DRN_ACT);   // vec_task.py:323-325
+    if (drn_mask & 2) dr_noise_apply<4>(av, a.drn[1], a.seed, gid, sc.step, RNG_DRN_ACT);   // vec_task.py:323-325
     float eff[4];
     const bool on = tp.fault && S.progress >= S.fonset;
 #pragma unroll
@@ -826,7 +840,7 @@ OUZ_DEV void env_core(const StepArgs& a, const StepCtx& sc, int i, uint32_t gid,
       if (rst) { th = 0.0f; eff[k] = 0.0f; }                        // thrusts/forces[reset] = 0
       S.thrust[k] = th;
     }
-    if (tp.dr) {   // the rotors' motorConstant scale (ouz_dr_physical OUZ_DRP_MOTOR_CONSTANT)
+    if (dr) {   // the rotors' motorConstant scale (ouz_dr_physical OUZ_DRP_MOTOR_CONSTANT)
 #pragma unroll
       for (int k = 0; k < 4; ++k) eff[k] *= S.dr_t;
     }
@@ -845,7 +859,8 @@ OUZ_DEV void env_core(const StepArgs& a, const StepCtx& sc, int i, uint32_t gid,
     float T;
     V3 tau;
     const V3 cmd = v3(0.0f, 0.0f, 1.0f);
-    R0 = quat_to_mat(S.q);
+    if constexpr (CARRY) R0 = *Rc;
+    else R0 = quat_to_mat(S.q);
     lee_position_R(R0, S.p, S.v, S.w, cmd, 0.0f, default_gains(), T, tau);
     float fz = 2.0f * kGravity * T;
     V3 dd = cmd - S.p;
@@ -989,21 +1004,26 @@ OUZ_DEV void env_core(const StepArgs& a, const StepCtx& sc, int i, uint32_t gid,
   // ---- physics: gym.simulate -> lumped rigid body, c.substeps sub-steps ----
   {
     // additive inertia DR adds the same sample to each diagonal entry: the zz scale follows from the xx scale
-    const float dr_iz = a.pdr.inertia_add ? 1.0f + (S.dr_i - 1.0f) * (c.ixx * c.inv_izz) : S.dr_i;
+    const float dr_iz = (!PLAIN && a.pdr.inertia_add) ? 1.0f + (S.dr_i - 1.0f) * (c.ixx * c.inv_izz) : S.dr_i;
     const V3 I = v3(c.ixx * S.dr_i, c.iyy * S.dr_i, c.izz * dr_iz);
-    const float inv_m = tp.dr ? 1.0f / (c.mass * S.dr_m) : c.inv_mass;
-    const V3 inv_I = tp.dr ? v3(1.0f / I.x, 1.0f / I.y, 1.0f / I.z) : v3(c.inv_ixx, c.inv_iyy, c.inv_izz);
+    const float inv_m = dr ? 1.0f / (c.mass * S.dr_m) : c.inv_mass;
+    const V3 inv_I = dr ? v3(1.0f / I.x, 1.0f / I.y, 1.0f / I.z) : v3(c.inv_ixx, c.inv_iyy, c.inv_izz);
     if constexpr (TGT == TGT_TRAJ && !SPW) platform_step<CTRL, TGT>(a, sc, gid, S);
-    if constexpr (CTRL == CTRL_RL) R0 = quat_to_mat(S.q);
+    if constexpr (CTRL == CTRL_RL) {
+      if constexpr (CARRY) R0 = *Rc;
+      else R0 = quat_to_mat(S.q);
+    }
     const DeckContact deck{TGT != TGT_GOAL, S.plat.x, S.plat.y, S.plat_v.x, S.plat_v.y};
-    const float h = c.dt / (float)c.substeps;
+    const int nsub = PLAIN ? 2 : c.substeps;
+    const float h = c.dt / (float)c.substeps;   // (PLAIN too: the run-time quotient, loop invariant, not a folded one)
     // sim_params gravity (gym.set_sim_params after apply_randomizations, vec_task.py:648-660): nominal unless DR'd
-    const V3 grav = (a.drn_mask & 4) ? gravity_dr(grav_dr_of(a.drn), a.seed, sc.step) : v3(0.0f, 0.0f, -kGravity);
-    if (c.substeps == 2)   // the configured sub-step count (EKFLeeLanded.yaml:29), unrolled
-      integrate_thrust_body<2>(S.p, S.q, S.v, S.w, R0, f_b.z, tau_b, inv_m, I, inv_I, h, c.wmax, deck, grav);
+    const V3 grav = (drn_mask & 4) ? gravity_dr(grav_dr_of(a.drn), a.seed, sc.step) : v3(0.0f, 0.0f, -kGravity);
+    M3* const R_out = CARRY ? Rc : nullptr;
+    if (nsub == 2)   // the configured sub-step count (EKFLeeLanded.yaml:29), unrolled
+      integrate_thrust_body<2>(S.p, S.q, S.v, S.w, R0, f_b.z, tau_b, inv_m, I, inv_I, h, c.wmax, deck, grav, 2, R_out);
     else
-      integrate_thrust_body<0>(S.p, S.q, S.v, S.w, R0, f_b.z, tau_b, inv_m, I, inv_I, h, c.wmax, deck, grav,
-                               c.substeps);
+      integrate_thrust_body<0>(S.p, S.q, S.v, S.w, R0, f_b.z, tau_b, inv_m, I, inv_I, h, c.wmax, deck, grav, nsub,
+                               R_out);
   }
 
   OUZ_STAMP(4, false);
@@ -1025,7 +1045,7 @@ OUZ_DEV void env_core(const StepArgs& a, const StepCtx& sc, int i, uint32_t gid,
     dist = target_dist(p, target);
     *post_target = target;
   } else {
-    obs_reward(a, sc, tp, task, gid, p, q, v, w, target, ob, rew, dist);
+    obs_reward<PLAIN>(a, sc, tp, task, gid, p, q, v, w, target, ob, rew, dist);
   }
   const bool timeout_len = S.progress >= tp.max_ep - 1;
   const bool die = dist > 8.0f || p.z < tp.z_die;
@@ -1038,7 +1058,7 @@ OUZ_DEV void env_core(const StepArgs& a, const StepCtx& sc, int i, uint32_t gid,
     }
   }
   S.rst = rs;
-  if (!OWV && a.trace_cap > 0 && i == a.trace_env) {   // trajectory CSV row (ekf_lee_landed.py:667-674)
+  if (!OWV && !PLAIN && a.trace_cap > 0 && i == a.trace_env) {   // trajectory CSV row (ekf_lee_landed.py:667-674)
     float* t = a.trace + (size_t)(sc.step % (uint32_t)a.trace_cap) * 9;
     t[0] = p.x; t[1] = p.y; t[2] = p.z;
     t[3] = target.x; t[4] = target.y; t[5] = target.z;
@@ -1180,6 +1200,14 @@ inline void fill_step_args(const ouz_config* cfg, StepArgs& a) {
     a.tp[tp_slot(t)] = tp;
   }
   if (preset_dr) a.pdr = derive_phys_dr(default_phys_dr(cfg));   // the DR tasks' flags stay their presets'
+}
+
+// The plain configuration of a launch of `task` (the PLAIN kernels): no physical DR for the task, no observation /
+// action noise and no gravity DR, no trajectory trace, the configured two sub-steps.  Every one of these can change
+// between launches (ouz_set_dr_physical, ouz_set_dr_noise, ouz_set_dr_gravity, ouz_set_trace), so it is evaluated
+// from the StepArgs of each launch.
+inline bool plain_config(const StepArgs& a, int task) {
+  return a.tp[tp_slot(task)].dr == 0 && a.drn_mask == 0 && a.trace_cap == 0 && a.c.substeps == 2;
 }
 
 // Waypoint tables of landing.py:108-112 (lemniscate(a=4,100), circle(r=2,100), square(4,8)),

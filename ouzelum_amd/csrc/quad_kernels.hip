@@ -166,6 +166,22 @@ __device__ __forceinline__ void emit(const OutPtrs& o, float* wave_lds, int i, i
   wave_lds_sync();
 }
 
+// The plain-config form of the output-wave rollouts (quad_env.h plain_config): the same results from a state-wave
+// loop without the code and the live StepArgs of options that are off; OUZ_PLAIN_ROLLOUT=0 keeps the general kernels.
+// LeeLanded: 98 -> 6 SGPR spills; 4096 envs, 32-step launches 1.48 -> 1.37 us per step, QuadFault 8192 envs +20 %
+// env-steps/s with the carried R(q) below (docs/HISTORY.md round 7, profiles/r07/ab_rounds.txt).
+constexpr bool kPlainDefault = true;
+__host__ __device__ constexpr bool plain_task(int task) {
+  return task == OUZ_TASK_LEE_LANDED || task == OUZ_TASK_OUZELUM || task == OUZ_TASK_FAULT;
+}
+// R(q) carried from a step's integrator to the next step in the output-wave rollouts (run_env CARRY);
+// -DOUZ_CARRY_R=0 forms it twice per step as the one-step kernels do (an A/B build, bitwise the same results;
+// LeeLanded 4096 envs 1.37 -> 1.30 us per step).
+#ifndef OUZ_CARRY_R
+#define OUZ_CARRY_R 1
+#endif
+constexpr bool kCarryR = OUZ_CARRY_R != 0;
+
 // The output wave of a latency-regime rollout.  The step's observation, reward, episode
 // statistics and output stores feed nothing the next step computes but the done flags, so a second wave of the
 // tile forms them from the post-step state while the state wave runs the next step's chain.  The state wave
@@ -222,8 +238,9 @@ struct LaneStats {
 // stepped by the workgroup's other wave (cov_wave), the two meet in `spl_lds`.
 // OWV: the state wave of a rollout with an output wave (out_wave): the step's outputs, episode tracking and
 // statistics are the output wave's; this wave publishes the post-step state into `orl` instead.
+// PLAIN: a plain-config launch (plain_config, quad_env.h; the output-wave rollouts of the tasks without the estimator).
 template <int CTRL, int TGT, bool MULTI, bool PRE = false, bool CLS = false, bool NTL = false, bool QLN = false,
-          bool SPW = false, bool OWV = false>
+          bool SPW = false, bool OWV = false, bool PLAIN = false>
 __device__ __forceinline__ void run_env(const StepArgs& a, const StepCtx* ctx, int K, const OutPtrs* outs,
                                         size_t out_stride, float* wave_lds, int i, int e, bool valid, int task,
                                         bool direct = false, int stats_mode = 0, LaneStats* ls = nullptr,
@@ -238,6 +255,10 @@ __device__ __forceinline__ void run_env(const StepArgs& a, const StepCtx* ctx, i
   SplitLane spl{spl_lds, 0, threadIdx.x & 63u};
   static_assert(!SPW || (MULTI && !PRE && !QLN && CTRL == CTRL_LEE_EST), "the split form is the estimator rollout's");
   static_assert(!OWV || (MULTI && !PRE && !QLN), "the output wave is the rollout's");
+  static_assert(!PLAIN || (OWV && !CLS && CTRL != CTRL_LEE_EST), "the plain form is the output-wave rollout's");
+  // The state wave of an output-wave rollout carries R(q) from a step's integrator to the next step's controller
+  // (env_core CARRY): its loop is one dependent chain, and the second quat_to_mat of the same quaternion was on it.
+  constexpr bool CARRY = kCarryR && OWV && CTRL != CTRL_LEE_EST;
   if constexpr (QLN) {
     static_assert(CTRL == CTRL_LEE_EST, "the quad-lane form is the estimator's");
     __shared__ double s_pv[16 * kPvLdsEnv];   // one 64-lane block = one wave = 16 envs
@@ -258,7 +279,7 @@ __device__ __forceinline__ void run_env(const StepArgs& a, const StepCtx* ctx, i
     ep_cnt_old = ldi(S.T, OUZ_I_EP_CNT);
     ep_len_old = ldi(S.T, OUZ_I_EP_LEN);
   }
-  if (valid) env_load<CTRL, TGT, CLS, NTL, QLN || SPW>(a, e, tp, S, ctx[0].actions);
+  if (valid) env_load<CTRL, TGT, CLS, NTL, QLN || SPW, PLAIN>(a, e, tp, S, ctx[0].actions);
   if constexpr (QLN) {
     if (valid) pv_lds_load(ql, [&](int f) { return ld(S.T, OUZ_F_PV_P + f); });
     ql_sync();
@@ -295,6 +316,10 @@ __device__ __forceinline__ void run_env(const StepArgs& a, const StepCtx* ctx, i
     __builtin_amdgcn_s_waitcnt(kWaitVmcnt0);
     const bool fc0 = S.flags_clear, rst0 = S.rst;   // OWV: step 0's flag / reset state, for the output wave
     int out_seen = 0;                               // OWV: the output wave's consumed count last seen
+    M3 Rc{};                                        // CARRY: quat_to_mat of the state quaternion
+    if constexpr (CARRY) {
+      if (valid) Rc = quat_to_mat(S.q);             // the first step's, from the loaded state
+    }
     for (int k = 0; k < K; ++k) {
       if (kStampSlots > 13 && k <= 16) OUZ_STAMP(13 + k, false);
       float ob[OUZ_NUM_OBS];
@@ -306,8 +331,8 @@ __device__ __forceinline__ void run_env(const StepArgs& a, const StepCtx* ctx, i
       spl.k = k;
       V3 post_target = v3(0.0f, 0.0f, 0.0f);
       if (valid)
-        env_core<CTRL, TGT, false, QLN, SPW, OWV>(a, ctx[k], e, gid, task, S, ob, rew, rs, to, nullptr, &ql, &spl,
-                                                  &post_target);
+        env_core<CTRL, TGT, false, QLN, SPW, OWV, PLAIN, CARRY>(a, ctx[k], e, gid, task, S, ob, rew, rs, to, nullptr,
+                                                                &ql, &spl, &post_target, &Rc);
       if (kStampSlots > 13 && k == 8) OUZ_STAMP(30, false);
       if (valid && k + 1 < K) load_actions<CTRL, TGT, CLS>(ctx[k + 1].actions, S, e);   // next step's row, before emit
       if constexpr (OWV) {   // (the reset counts of the trajectory log are the output wave's)
@@ -372,7 +397,7 @@ __device__ __forceinline__ void run_env(const StepArgs& a, const StepCtx* ctx, i
 // stores of run_env's one-wave loop, from the state wave's published post-step state; at the end the episode
 // fields and the fused statistics.  Same functions (obs_reward, emit / emit_env) on the same values: the
 // outputs are bitwise those of the one-wave rollout.
-template <bool CLS>
+template <bool CLS, bool PLAIN = false>
 __device__ __forceinline__ void out_wave(const StepArgs& a, const StepCtx* ctx, int K, const OutPtrs* outs,
                                          size_t out_stride, float* wave_lds, int i, int e, bool valid, int task,
                                          int stats_mode, LaneStats* ls, OutRingLds& R) {
@@ -406,20 +431,20 @@ __device__ __forceinline__ void out_wave(const StepArgs& a, const StepCtx* ctx, 
     const bool rs = (meta & 1) != 0, to = (meta & 2) != 0;
     // run_env's trajectory-log reset count: the step's resets are the envs its previous step ended (step 0:
     // the buffers' own flags)
-    trace_count(a, ctx[k].step, vout && (k == 0 ? (meta & 8) != 0 : prev_rs), i, e);
+    if constexpr (!PLAIN) trace_count(a, ctx[k].step, vout && (k == 0 ? (meta & 8) != 0 : prev_rs), i, e);
     // run_env's flag state: at step 0 the buffers' own, later "not reset by the previous step"
     const bool flags_clear = vout && (k == 0 ? (meta & 4) != 0 : !prev_rs);
     float ob[OUZ_NUM_OBS];
     float rew = 0.0f;
     if (valid) {
-      if (a.trace_cap > 0 && e == a.trace_env) {   // env_core's trajectory CSV row (ekf_lee_landed.py:667-674)
+      if (!PLAIN && a.trace_cap > 0 && e == a.trace_env) {   // env_core's trajectory CSV row (ekf_lee_landed.py:667-674)
         float* t = a.trace + (size_t)(ctx[k].step % (uint32_t)a.trace_cap) * 9;
         t[0] = p.x; t[1] = p.y; t[2] = p.z;
         t[3] = target.x; t[4] = target.y; t[5] = target.z;
         t[6] = v.x; t[7] = v.y; t[8] = v.z;
       }
       float dist;
-      obs_reward(a, ctx[k], tp, task, gid, p, q, v, w, target, ob, rew, dist);
+      obs_reward<PLAIN>(a, ctx[k], tp, task, gid, p, q, v, w, target, ob, rew, dist);
       if (a.track_episodes) {   // RecordEpisodeStatisticsTorch.step (PPO/utils.py:20-35), as env_core
         ep_ret += rew;
         if (rs) { ep_sum_add += ep_ret; ep_cnt_add += 1; ep_len_add += progress; ep_ret = 0.0f; }
@@ -639,7 +664,7 @@ __device__ __forceinline__ int mixed_task_tile(const StepArgs& a, int task, int 
 }
 
 template <int TASK, bool MULTI, bool PRE = false, bool CLS = false, bool NTL = false, bool QUAD = false,
-          bool SPW = false, bool OWV = false, bool MIXT = false>
+          bool SPW = false, bool OWV = false, bool MIXT = false, bool PLAIN = false>
 __device__ __forceinline__ void step_body(const StepArgs& a, const StepCtx* ctx, int K, const OutPtrs* outs,
                                           uint64_t out_stride, const RolloutStats* rst = nullptr,
                                           float* wrench = nullptr) {
@@ -653,6 +678,7 @@ __device__ __forceinline__ void step_body(const StepArgs& a, const StepCtx* ctx,
     // wave forms the outputs (out_wave).
     static_assert(MULTI && !PRE && !QUAD, "the multi-wave forms are the rollout's");
     static_assert(!SPW || quad_lane_kernel(TASK, CLS), "the split form is the estimator's class layout");
+    static_assert(!PLAIN || (OWV && !SPW && !CLS && plain_task(TASK)), "the plain form: plain_task's output-wave rollouts");
     SplitPvLds* spl = nullptr;
     OutRingLds* orl = nullptr;
     if constexpr (SPW) {
@@ -690,10 +716,10 @@ __device__ __forceinline__ void step_body(const StepArgs& a, const StepCtx* ctx,
     constexpr int kOutRole = SPW ? 2 : 1;
     if (role == 0) {
       if constexpr (TASK == OUZ_TASK_OUZELUM || TASK == OUZ_TASK_FAULT)
-        run_env<CTRL_RL, TGT_GOAL, true, false, CLS, false, false, false, OWV>(
+        run_env<CTRL_RL, TGT_GOAL, true, false, CLS, false, false, false, OWV, PLAIN>(
             a, ctx, K, outs, out_stride, wave_lds, i, e, valid, TASK, false, sm, &ls, nullptr, nullptr, orl);
       else if constexpr (TASK == OUZ_TASK_LEE_LANDED)
-        run_env<CTRL_LEE_TRUE, TGT_PLATFORM, true, false, CLS, false, false, false, OWV>(
+        run_env<CTRL_LEE_TRUE, TGT_PLATFORM, true, false, CLS, false, false, false, OWV, PLAIN>(
             a, ctx, K, outs, out_stride, wave_lds, i, e, valid, TASK, false, sm, &ls, nullptr, nullptr, orl);
       else if constexpr (TASK == OUZ_TASK_LANDING)
         run_env<CTRL_RL, TGT_TRAJ, true, false, CLS, false, false, false, OWV>(
@@ -721,7 +747,7 @@ __device__ __forceinline__ void step_body(const StepArgs& a, const StepCtx* ctx,
       if (run_task == OUZ_TASK_TRACKING || run_task == OUZ_TASK_EKF_LEE_LANDED)
         cov_wave(a, ctx, K, i, e, valid, *spl);
     } else if (OWV && role == kOutRole) {
-      out_wave<CLS>(a, ctx, K, outs, out_stride, wave_lds, i, e, valid, run_task, sm, &ls, *orl);
+      out_wave<CLS, PLAIN>(a, ctx, K, outs, out_stride, wave_lds, i, e, valid, run_task, sm, &ls, *orl);
       if (sm) reduce_stats(*rst, blockIdx.x, gridDim.x, ls);   // the output waves of the exact grid
     }
     return;
@@ -857,12 +883,13 @@ __global__ void __launch_bounds__(kMaxBlock) quad_pre_kernel(StepArgs a, StepCtx
 // idle a third of the time; at two waves per SIMD the compiler spills ~90 VGPRs to scratch (L1/L2-resident) and
 // the rollout runs 10-12 % faster per step at 4 M envs (QuadTracking 410 -> 359 us, QuadMixed 380 -> 344:
 // profiles/r04/wide_rollout_ab.txt).
+// PLAIN: the plain-config form (plain_config; launch_task picks it per launch).
 template <int TASK, bool CLS = false, bool QUAD = false, bool SPW = false, bool OWV = false, int WPE = 1,
-          bool MIXT = false>
+          bool MIXT = false, bool PLAIN = false>
 __global__ void __launch_bounds__(kMaxBlock) __attribute__((amdgpu_waves_per_eu(WPE)))
 quad_rollout_kernel(StepArgs a, RolloutArgs r) {
   prefetch_kernargs<(int)(sizeof(StepArgs) + sizeof(RolloutArgs) + 8)>();
-  step_body<TASK, true, false, CLS, false, QUAD, SPW, OWV, MIXT>(a, r.ctx, r.K, r.outs, r.out_stride, &r.stats);
+  step_body<TASK, true, false, CLS, false, QUAD, SPW, OWV, MIXT, PLAIN>(a, r.ctx, r.K, r.outs, r.out_stride, &r.stats);
 }
 #ifndef OUZ_EST_ROLLOUT_WPE
 #define OUZ_EST_ROLLOUT_WPE 2   // (A/B builds: -DOUZ_EST_ROLLOUT_WPE=3)
@@ -1510,6 +1537,9 @@ int ouz_create(const ouz_config* cfg, ouz_env** out) {
     // (the mixed curriculum has the output-wave form in its class layout only)
     const bool ow_size = a.n_slots <= kOutWaveMaxSlots && !a.quad && (a.cls || cfg->task != OUZ_TASK_MIXED);
     a.outw = (ow_size && (ow ? std::atoi(ow) != 0 : kOutWaveDefault)) ? 1 : 0;
+    // the plain-config kernels of those rollouts, chosen per launch (launch_task); OUZ_PLAIN_ROLLOUT=0 / 1 overrides
+    const char* pl = std::getenv("OUZ_PLAIN_ROLLOUT");
+    a.plain = (pl ? std::atoi(pl) != 0 : kPlainDefault) ? 1 : 0;
   }
   {
     const char* rs = std::getenv("OUZ_ROLLOUT_STREAM");
@@ -1591,8 +1621,16 @@ static void launch_task(bool single, const StepArgs& a, const RolloutArgs& r, di
   }
   if (single && a.nt_loads) hipLaunchKernelGGL((quad_step_kernel<T, false, true>), g, b, 0, s, a, r.ctx[0]);
   else if (single) hipLaunchKernelGGL((quad_step_kernel<T, false, false>), g, b, 0, s, a, r.ctx[0]);
-  else if (T != OUZ_TASK_MIXED && a.outw)
+  else if (T != OUZ_TASK_MIXED && a.outw) {
+    // the plain form where this launch's configuration allows it: the options it leaves out can be set between launches
+    if constexpr (plain_task(T)) {
+      if (a.plain && plain_config(a, T)) {
+        hipLaunchKernelGGL((quad_rollout_kernel<T, false, false, false, true, 1, false, true>), g, dim3(128), 0, s, a, r);
+        return;
+      }
+    }
     hipLaunchKernelGGL((quad_rollout_kernel<T, false, false, false, T != OUZ_TASK_MIXED>), g, dim3(128), 0, s, a, r);
+  }
   else if (class_layout_task(T) && rollout_wpe(T, a.n) > 1)
     hipLaunchKernelGGL((quad_rollout_kernel<T, false, false, false, false, (class_layout_task(T) ? OUZ_EST_ROLLOUT_WPE : 1)>), g, b,
                        0, s, a, r);

@@ -829,9 +829,12 @@ OUZ_HD void integrate(V3& p, Q4& q, V3& v, V3& w, V3 f_b, V3 tau_b, float inv_m,
 // controller), R(q)'s third column between sub-steps and R(q) once at exit for the world-frame w.
 // |w| = |w_b| (the clamp) and w = 0 <=> w_b = 0 (the deck) carry over unchanged.
 // NSUB > 0: that many sub-steps, unrolled; NSUB = 0: nsub sub-steps in a loop.  g: the gravity vector.
+// R_out (optional): receives R(q) of the post-step quaternion, formed here for the world-frame body rate (the fused
+// rollout hands it to its next step as R0).
 template <int NSUB>
 OUZ_HD void integrate_thrust_body(V3& p, Q4& q, V3& v, V3& w, const M3& R0, float fz, V3 tau_b, float inv_m, V3 I,
-                                  V3 inv_I, float h, float wmax, DeckContact deck, V3 g, int nsub = NSUB) {
+                                  V3 inv_I, float h, float wmax, DeckContact deck, V3 g, int nsub = NSUB,
+                                  M3* R_out = nullptr) {
   V3 wb = mtv(R0, w);
   V3 z = v3(R0.m[2], R0.m[5], R0.m[8]);
   const float acc = fz * inv_m;
@@ -876,7 +879,9 @@ OUZ_HD void integrate_thrust_body(V3& p, Q4& q, V3& v, V3& w, const M3& R0, floa
       q = Q4{q.x * qi, q.y * qi, q.z * qi, q.w * qi};
     }
   }
-  w = mv(quat_to_mat(q), wb);
+  const M3 R1 = quat_to_mat(q);
+  w = mv(R1, wb);
+  if (R_out) *R_out = R1;
 }
 
 }  // namespace ouz
