@@ -159,6 +159,11 @@ struct EnvConsts {
   int32_t substeps, conv_time;
   float mass, ixx, iyy, izz;
   float inv_mass, inv_ixx, inv_iyy, inv_izz;
+  // plat_speed / kWheelRadius, the husky's wheel-speed limit, divided once on the host.  As `c.plat_speed /
+  // kWheelRadius` in platform_step the quotient was the correctly rounded division where the compiler hoisted it
+  // out of a rollout's step loop and the build's approximate one (a multiply by 1 / kWheelRadius) in the one-step
+  // kernels, one ulp apart: the fused rollouts and VecTask.step drove the platform at different saturated speeds.
+  float plat_wmax;
 };
 
 // Physical domain randomisation as the step reads it (include/ouzelum.h ouz_dr_physical): the ABI parameters and
@@ -706,7 +711,7 @@ OUZ_DEV void platform_step(const StepArgs& a, const StepCtx& sc, uint32_t gid,
   float lin = sqrtf(dx * dx + dy * dy) * kDriveGainLin, ang = dth * kDriveGainAng;
   const float wl = (2.0f * lin + ang * kWheelBase) / (2.0f * kWheelRadius);
   const float wr = (2.0f * lin - ang * kWheelBase) / (2.0f * kWheelRadius);
-  const float mx = fmaxf(fabsf(wl), fabsf(wr)), max_w = c.plat_speed / kWheelRadius;
+  const float mx = fmaxf(fabsf(wl), fabsf(wr)), max_w = c.plat_wmax;
   if (mx > max_w) { const float scl = max_w / mx; lin *= scl; ang *= scl; }
   th = map_to_pi(th + ang * c.dt);
   float sn, cs;
@@ -861,7 +866,7 @@ OUZ_DEV void env_core(const StepArgs& a, const StepCtx& sc, int i, uint32_t gid,
     const V3 cmd = v3(0.0f, 0.0f, 1.0f);
     if constexpr (CARRY) R0 = *Rc;
     else R0 = quat_to_mat(S.q);
-    lee_position_R(R0, S.p, S.v, S.w, cmd, 0.0f, default_gains(), T, tau);
+    lee_position_R<true>(R0, S.p, S.v, S.w, cmd, 0.0f, default_gains(), T, tau);
     float fz = 2.0f * kGravity * T;
     V3 dd = cmd - S.p;
     if (sqrtf(dot(dd, dd)) < tp.land_radius) {
@@ -980,8 +985,8 @@ OUZ_DEV void env_core(const StepArgs& a, const StepCtx& sc, int i, uint32_t gid,
       OUZ_STAMP(6, false);
       pv_split_correct(*spl, xd, S.px, g % 7u == 6u, v3(pm[0], pm[1], pm[2]), g % 3u == 0u, v3(vm[0], vm[1], vm[2]));
     }
-    if (conv) lee_position_R(R0, S.p, S.v, S.w, wp, 0.0f, default_gains(), T, tau);
-    else lee_position_R(R0, v3(S.px[0], S.px[1], S.px[2]), v3(S.px[3], S.px[4], S.px[5]), S.w, wp, 0.0f, default_gains(), T, tau);
+    if (conv) lee_position_R<true>(R0, S.p, S.v, S.w, wp, 0.0f, default_gains(), T, tau);
+    else lee_position_R<true>(R0, v3(S.px[0], S.px[1], S.px[2]), v3(S.px[3], S.px[4], S.px[5]), S.w, wp, 0.0f, default_gains(), T, tau);
     float fz = 2.0f * kGravity * T;
     if (td < tp.land_radius) {                       // :508-515
       if (!conv) { S.land_flag = 1; S.dirty |= D_LAND; }
@@ -1020,7 +1025,7 @@ OUZ_DEV void env_core(const StepArgs& a, const StepCtx& sc, int i, uint32_t gid,
     const V3 grav = (drn_mask & 4) ? gravity_dr(grav_dr_of(a.drn), a.seed, sc.step) : v3(0.0f, 0.0f, -kGravity);
     M3* const R_out = CARRY ? Rc : nullptr;
     if (nsub == 2)   // the configured sub-step count (EKFLeeLanded.yaml:29), unrolled
-      integrate_thrust_body<2>(S.p, S.q, S.v, S.w, R0, f_b.z, tau_b, inv_m, I, inv_I, h, c.wmax, deck, grav, 2, R_out);
+      integrate_thrust_body<2, PLAIN>(S.p, S.q, S.v, S.w, R0, f_b.z, tau_b, inv_m, I, inv_I, h, c.wmax, deck, grav, 2, R_out);
     else
       integrate_thrust_body<0>(S.p, S.q, S.v, S.w, R0, f_b.z, tau_b, inv_m, I, inv_I, h, c.wmax, deck, grav, nsub,
                                R_out);
@@ -1185,7 +1190,8 @@ inline void fill_step_args(const ouz_config* cfg, StepArgs& a) {
   a.c = EnvConsts{cfg->dt, (float)((double)cfg->dt * (double)cfg->thrust_rate), cfg->thrust_max, cfg->plat_speed,
                   cfg->dr_lo, cfg->dr_hi, cfg->fault_eta_hi, (float)(4.0 * 3.14159265358979323846),
                   cfg->substeps, cfg->convergence_time, (float)mass, (float)ixx, (float)ixx, (float)izz,
-                  1.0f / (float)mass, 1.0f / (float)ixx, 1.0f / (float)ixx, 1.0f / (float)izz};
+                  1.0f / (float)mass, 1.0f / (float)ixx, 1.0f / (float)ixx, 1.0f / (float)izz,
+                  cfg->plat_speed / kWheelRadius};
   bool preset_dr = false;
   for (int t = 0; t < OUZ_NUM_TASKS; ++t) {
     if (!task_used(cfg->task, t)) continue;
@@ -1206,8 +1212,13 @@ inline void fill_step_args(const ouz_config* cfg, StepArgs& a) {
 // action noise and no gravity DR, no trajectory trace, the configured two sub-steps.  Every one of these can change
 // between launches (ouz_set_dr_physical, ouz_set_dr_noise, ouz_set_dr_gravity, ouz_set_trace), so it is evaluated
 // from the StepArgs of each launch.
+// Small-angle sub-steps: the clamp (or the deck contact) leaves n2 <= wmax^2, so a sub-step's half angle is
+// th = 0.5 h sqrtf(n2) <= 0.5 h wmax (1 + a few ulp); the build's sqrtf (-fno-hip-fp32-correctly-rounded-divide-sqrt) is
+// within 2 ulp and the factor 1.01 covers that and the products' roundings with room to spare.  Under this bound
+// the integrator's `th < 0.04f` test is always true (0.0314 at the configured dt) and the PLAIN kernels drop it.
 inline bool plain_config(const StepArgs& a, int task) {
-  return a.tp[tp_slot(task)].dr == 0 && a.drn_mask == 0 && a.trace_cap == 0 && a.c.substeps == 2;
+  const bool small_angle = 0.5f * (a.c.dt / (float)a.c.substeps) * a.c.wmax * 1.01f < 0.04f;
+  return a.tp[tp_slot(task)].dr == 0 && a.drn_mask == 0 && a.trace_cap == 0 && a.c.substeps == 2 && small_angle;
 }
 
 // Waypoint tables of landing.py:108-112 (lemniscate(a=4,100), circle(r=2,100), square(4,8)),

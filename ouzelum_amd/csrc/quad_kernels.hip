@@ -20,7 +20,6 @@
 #include <string>
 
 #include "../../include/ouzelum.h"
-#include "quad_math.h"
 
 #define OUZ_SCHED_FENCE() __builtin_amdgcn_sched_barrier(0)
 
@@ -55,6 +54,7 @@ constexpr int kStampSlots = 0;
 #endif
 #define OUZ_QL_STAMP(k) OUZ_STAMP(k, true)
 }  // namespace ouz
+#include "quad_math.h"   // after OUZ_STAMP: the integrator stamps its sub-step boundary in the probe build
 #include "quad_pv_ql.h"
 #include "quad_pv_split.h"
 #include "quad_env.h"

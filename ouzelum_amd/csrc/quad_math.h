@@ -21,6 +21,13 @@
 
 #include "philox.h"
 
+// The probe build of the kernels (-DOUZ_STAMPS) defines OUZ_STAMP before this file; every other build stamps nothing.
+#ifdef OUZ_STAMP
+#define OUZ_SUBSTEP_STAMP(k) OUZ_STAMP(k, false)
+#else
+#define OUZ_SUBSTEP_STAMP(k) do {} while (0)
+#endif
+
 namespace ouz {
 
 // ---------------------------------------------------------------------------
@@ -135,10 +142,14 @@ OUZ_HD M3 quat_to_mat(Q4 q) {
 // controller needs the yaw angle itself (its yaw-rate error, :89-92).
 struct EulerSC { float sr, cr, sp, cp, sy, cy; };
 
+// Selects, not a branch: the quotient is formed for every lane and 0 * inf is discarded where h2 == 0, so the
+// values are the branch form's and the controller around the two calls stays one basic block.
 OUZ_HD void unit2(float y, float x, float& s, float& c) {
-  float h2 = x * x + y * y;
-  if (h2 > 0.0f) { float ih = 1.0f / sqrtf(h2); s = y * ih; c = x * ih; }
-  else { s = 0.0f; c = 1.0f; }     // atan2(0, 0) = 0
+  const float h2 = x * x + y * y;
+  const bool ok = h2 > 0.0f;
+  const float ih = 1.0f / sqrtf(h2);
+  s = ok ? y * ih : 0.0f;     // atan2(0, 0) = 0
+  c = ok ? x * ih : 1.0f;
 }
 
 OUZ_HD EulerSC euler_sc(const M3& R) {
@@ -201,6 +212,12 @@ OUZ_HD float remainder_f(float a, float b) {
   if (m != 0.0f && ((b < 0.0f) != (m < 0.0f))) m += b;
   return m;
 }
+// remainder_f under the precondition |a| < b (or a NaN): fmod(a, b) is a itself, so only the sign shift is left.
+OUZ_HD float remainder_small_f(float a, float b) {
+  float m = a;
+  if (m != 0.0f && ((b < 0.0f) != (m < 0.0f))) m += b;
+  return m;
+}
 
 // Shared attitude loop (position_control.py:66-108): returns torque.
 OUZ_HD V3 lee_attitude_loop(const M3& R, const M3& Rd, V3 omega, const EulerSC& e, float yaw_rate,
@@ -225,6 +242,10 @@ OUZ_HD V3 lee_attitude_loop(const M3& R, const M3& Rd, V3 omega, const EulerSC& 
 // LeePositionController.__call__ (controllers/position_control.py:19-109).
 // cmd = (x, y, z, yaw); thrust in units of m*g, torque "inertia normalised".
 // R = quat_to_mat(q) of the state quaternion (the step kernel shares it with the integrator).
+// kZeroYaw: the caller passes cmd_yaw == 0 (every step path).  Then the yaw error is -atan2f(..), |atan2f| <= pi_f32 <
+// 2 pi_f32, and the remainder needs no fmodf: the same value without the libm expansion (two loops, an f64 convert)
+// sitting between the yaw and the controller body.  The C-ABI controller entry takes any yaw command: false.
+template <bool kZeroYaw = false>
 OUZ_HD void lee_position_R(const M3& R, V3 p, V3 v, V3 w, V3 cmd_p, float cmd_yaw, const LeeGains& g,
                            float& thrust, V3& torque) {
   EulerSC e = euler_sc(R);
@@ -236,7 +257,8 @@ OUZ_HD void lee_position_R(const M3& R, V3 p, V3 v, V3 w, V3 cmd_p, float cmd_ya
   b2 = (1.0f / norm(b2)) * b2;
   V3 b1 = cross(b2, b3);
   M3 Rd{{b1.x, b2.x, b3.x, b1.y, b2.y, b3.y, b1.z, b2.z, b3.z}};
-  float yr = remainder_f(cmd_yaw - atan2f(R.m[3], R.m[0]), kTwoPiF);
+  const float ya = cmd_yaw - atan2f(R.m[3], R.m[0]);
+  float yr = kZeroYaw ? remainder_small_f(ya, kTwoPiF) : remainder_f(ya, kTwoPiF);
   if (yr > kPiF) yr -= kTwoPiF;
   torque = lee_attitude_loop(R, Rd, w, e, yr, g);
 }
@@ -831,7 +853,9 @@ OUZ_HD void integrate(V3& p, Q4& q, V3& v, V3& w, V3 f_b, V3 tau_b, float inv_m,
 // NSUB > 0: that many sub-steps, unrolled; NSUB = 0: nsub sub-steps in a loop.  g: the gravity vector.
 // R_out (optional): receives R(q) of the post-step quaternion, formed here for the world-frame body rate (the fused
 // rollout hands it to its next step as R0).
-template <int NSUB>
+// SMALL: the launch guarantees 0.5 h wmax < 0.04 with margin (plain_config, quad_env.h): |w_b| <= wmax after the clamp
+// (or 0 on the deck), so every sub-step takes the series side of the angle test and that side is the only code.
+template <int NSUB, bool SMALL = false>
 OUZ_HD void integrate_thrust_body(V3& p, Q4& q, V3& v, V3& w, const M3& R0, float fz, V3 tau_b, float inv_m, V3 I,
                                   V3 inv_I, float h, float wmax, DeckContact deck, V3 g, int nsub = NSUB,
                                   M3* R_out = nullptr) {
@@ -839,6 +863,8 @@ OUZ_HD void integrate_thrust_body(V3& p, Q4& q, V3& v, V3& w, const M3& R0, floa
   V3 z = v3(R0.m[2], R0.m[5], R0.m[8]);
   const float acc = fz * inv_m;
   for (int s = 0; s < (NSUB > 0 ? NSUB : nsub); ++s) {   // a constant NSUB unrolls by itself
+    // probe build: the boundary between the plain kernels' two sub-steps (slot 5 is the estimator's otherwise)
+    if (SMALL && s == 1) OUZ_SUBSTEP_STAMP(5);
     if (s > 0)   // third column of R(q) for the unit quaternion q (normalised at the end of every sub-step)
       z = v3(2.0f * (q.x * q.z + q.y * q.w), 2.0f * (q.y * q.z - q.x * q.w), 1.0f - 2.0f * (q.x * q.x + q.y * q.y));
     // g: the sim's gravity, (0, 0, -kGravity) unless sim_params DR'd (with g.x = g.y = 0 the x / y terms round as
@@ -861,7 +887,7 @@ OUZ_HD void integrate_thrust_body(V3& p, Q4& q, V3& v, V3& w, const M3& R0, floa
     const float n = sqrtf(n2);
     const float th = 0.5f * h * n, th2 = th * th;
     float sc, co;
-    if (th < 0.04f) {
+    if (SMALL || th < 0.04f) {
       // |w| <= 4 pi at the configured dt keeps th <= 0.0315: the series to th^2 (sin) / th^4 (cos) is
       // exact in f32 there (the next terms are < 1e-8 relative)
       sc = 0.5f * h * (1.0f - th2 * (1.0f / 6.0f));

@@ -1,7 +1,8 @@
 """Per-step timeline of the fused rollout kernel from per-wave s_memtime stamps (probe build with
 -DOUZ_STAMPS, loaded through OUZ_LIB).  Slots 13..29: start of rollout steps 0..16 (29 = after the
 last step); 30 / 31: mid-rollout step (k = 8) after env_core / after its stores were issued; 2 / 3 / 4: the
-last step's reset-done / controller-done / physics-done.
+last step's reset-done / controller-done / physics-done; 5: in the plain-config kernels, the boundary between
+the two sub-steps.
 
     OUZ_LIB=ouzelum_amd/libouzelum_probe.so python scripts/stamp_rollout.py LeeLanded 4096 [waves per tile]
 
@@ -80,6 +81,10 @@ if not (st[:, 2:5] > 0).all():
 else:
   print(f"  last step: prelude+reset {np.median(st[:, 2] - last):.0f}, controller {np.median(st[:, 3] - st[:, 2]):.0f}, "
       f"physics {np.median(st[:, 4] - st[:, 3]):.0f}, post+emit {np.median(st[:, 29] - st[:, 4]):.0f}")
+if (st[:, 2:6] > 0).all() and not (st[:, 10:13] > 0).any():
+    # the plain kernels stamp the boundary between their two sub-steps (slot 5; the estimator's slot otherwise)
+    print(f"  last step physics: sub-step 1 {np.median(st[:, 5] - st[:, 3]):.0f}, sub-step 2 + R(q), world-frame rate "
+          f"{np.median(st[:, 4] - st[:, 5]):.0f}")
 if (st[:, 10:13] > 0).all() and (st[:, 2:5] > 0).all():
     print(f"  last step estimator: inputs->EKF {np.median(st[:, 10] - st[:, 2]):.0f}, EKF {np.median(st[:, 11] - st[:, 10]):.0f}, "
           f"PV {np.median(st[:, 12] - st[:, 11]):.0f}, guidance+Lee {np.median(st[:, 3] - st[:, 12]):.0f}")
