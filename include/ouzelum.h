@@ -50,6 +50,8 @@
  *   ouz_reward      compute_ingenuity_reward   tasks/ekf_lee_landed.py:692-723
  *   ouz_philox      the counter RNG every draw of the step uses (replaces torch_rand_float /
  *                   torch.rand: ekf_lee_landed.py:284-286, ouzelum.py:183-184, utils/POMDP.py:25,30)
+ *   ouz_episode_step  RecordEpisodeStatisticsTorch.step on the learner's side (PPO/utils.py:20-35) and the
+ *                   per-env writer.add_scalar loop over the finished episodes (PPO/main.py:98-103)
  */
 #ifndef OUZELUM_H_
 #define OUZELUM_H_
@@ -60,7 +62,7 @@
 extern "C" {
 #endif
 
-#define OUZ_ABI_VERSION 6   /* 2: trigger-class state layout of the estimator tasks (ouz_state_slots);
+#define OUZ_ABI_VERSION 7  /* 2: trigger-class state layout of the estimator tasks (ouz_state_slots);
                                3: 1344-id curriculum chunks of OUZ_TASK_MIXED with the class layout, ouz_env_slots;
                                4: physical domain randomisation (ouz_dr_physical, OUZ_I_RAND_STEP), DR noise
                                   frequency (ouz_dr_noise.frequency);
@@ -68,7 +70,9 @@ extern "C" {
                                   ouz_policy_sample);
                                6: sim_params gravity domain randomisation (ouz_set_dr_gravity), the fused LSTM
                                   sequence kernels (ouz_lstm_seq_fwd / ouz_lstm_seq_bwd), clipped Adam
-                                  (ouz_adam_clip_step), the small-K first layer (ouz_linear_tanh_small_k) */
+                                  (ouz_adam_clip_step), the small-K first layer (ouz_linear_tanh_small_k);
+                               7: per-env episode statistics with the per-episode record append (ouz_episode_step,
+                                  ouz_episode_record) */
 
 /* error codes */
 #define OUZ_OK 0
@@ -401,6 +405,21 @@ int ouz_gae(const float* rewards, const float* values, const float* dones, const
  * keyed (seed, row_offset + row, call); in == out is allowed. */
 int ouz_pomdp_obs(const float* in, float* out, int32_t rows, int32_t dim, int32_t mode, float prob, uint64_t seed,
                   int64_t row_offset, uint32_t call, void* stream);
+
+/* RecordEpisodeStatisticsTorch.step (PPO/utils.py:20-35, RPO-LSTM/utils.py:20-34) in one launch, with the append
+ * of the per-episode points the learners log (PPO/main.py:98-103, RPO-LSTM/main.py:105-110).  Per env i < n, each
+ * operation rounded as torch's f32 / i32 one:  ep_ret += rew; ep_len += 1; ret_out = ep_ret; len_out = ep_len;
+ * ep_ret *= (float)(1 - done); ep_len *= (1 - done)  (the reference's multiplication: a negative return of a
+ * finished episode leaves -0.0, a NaN stays NaN).  done is int64, as VecTask.step returns it.
+ * With records non-null every env with done != 0 appends {tag, env_id0 + i, ret_out, len_out} at a slot taken from
+ * *count (one device-scope atomic add per wave; slots within a launch land in no fixed order: sort by (tag,
+ * env_id)).  count accumulates across launches (the caller zeroes it, once per rollout); a record whose slot is at
+ * or beyond capacity is not stored while count still grows, so count > capacity tells the host of the overflow.
+ * records null: statistics only, count untouched.  records 16-byte aligned, capacity > 0. */
+typedef struct { int32_t tag; int32_t env_id; float ret; int32_t len; } ouz_episode_record;   /* 16 bytes */
+int ouz_episode_step(const float* rew, const int64_t* done, float* ep_ret, int32_t* ep_len, float* ret_out,
+                     int32_t* len_out, int32_t n, int32_t tag, int32_t env_id0, ouz_episode_record* records,
+                     int32_t capacity, uint32_t* count, void* stream);
 
 /* Fused LSTM cell for the recurrent actor (RPO-LSTM/model.py:27-50; torch gate order
  * i, f, g, o).  gates [B][4H] = x W_ih^T + b + (keep * h) W_hh^T, pre-activation;

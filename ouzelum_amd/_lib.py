@@ -25,7 +25,7 @@ class OuzelumError(RuntimeError):
 
 
 # --- constants mirrored from include/ouzelum.h (checked against the library in tests) ---
-ABI_VERSION = 6
+ABI_VERSION = 7
 LAYOUT_VERSION = 4  # the ABI version whose state-slot rules (include/ouzelum.h "State slots") the layout follows
 TASK_OUZELUM, TASK_LEE_LANDED, TASK_EKF_LEE_LANDED, TASK_TRACKING, TASK_FAULT, TASK_MIXED, TASK_LANDING = range(7)
 NUM_TASKS = 7
@@ -102,6 +102,10 @@ class OuzAdamTable(ctypes.Structure):
                 ("exp_avg_sq", ctypes.c_void_p * ADAM_MAX_TENSORS)]
 
 
+class OuzEpisodeRecord(ctypes.Structure):   # ouz_episode_record, 16 bytes
+    _fields_ = [("tag", ctypes.c_int32), ("env_id", ctypes.c_int32), ("ret", ctypes.c_float), ("len", ctypes.c_int32)]
+
+
 _P = ctypes.c_void_p
 _I = ctypes.c_int32
 _F = ctypes.c_float
@@ -152,6 +156,7 @@ SIGNATURES = {
     "ouz_philox": (_I, [_U64, _P, _U32, _U32, _U32, _P, _I, _P]),
     "ouz_gae": (_I, [_P, _P, _P, _P, _P, _I, _I, _F, _F, _P, _P, _P]),
     "ouz_pomdp_obs": (_I, [_P, _P, _I, _I, _I, _F, _U64, _I64, _U32, _P]),
+    "ouz_episode_step": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _I, _P, _P]),
     "ouz_lstm_cell_fwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P]),
     "ouz_lstm_cell_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P]),
     "ouz_lstm_seq_pack": (_I, [_P, _I, _P, _P, _P]),

@@ -8,6 +8,8 @@
 //  * ouz_pomdp_obs: the learner's POMDPWrapper.observation (utils/POMDP.py:23-43)
 //    on device with the counter RNG, keyed (seed, global row, call index), instead
 //    of a CPU torch.rand coin + a CPU noise tensor copied H2D every step.
+//  * ouz_episode_step: the learner-side episode statistics (PPO/utils.py:20-35) and the
+//    records of the episodes that end at this step, one launch and no host read.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -71,6 +73,53 @@ __global__ void __launch_bounds__(256) pomdp_obs_kernel(const float* __restrict_
         y[e] = v;
       }
     }
+  }
+}
+
+// ---------------------------------------------------------------------------
+// RecordEpisodeStatisticsTorch.step (PPO/utils.py:20-35) in one launch instead of seven torch ones, plus the append
+// of the finished episodes' {tag, env id, return, length} that the reference logs one .item() at a time
+// (PPO/main.py:98-103).  The append is wave-aggregated: ballot of the done lanes, one device-scope atomicAdd of
+// their count by the first done lane, its result broadcast, each lane's slot = base + done lanes below it, one
+// 16-byte store per record.  Lanes at or beyond n stay in the wave as "not done" up to the ballot (no early return:
+// the ragged last wave would otherwise ballot over exited lanes).
+// ---------------------------------------------------------------------------
+static_assert(sizeof(ouz_episode_record) == 16, "one 16-byte store per record");
+
+__global__ void __launch_bounds__(256) episode_step_kernel(const float* __restrict__ rew,
+                                                           const int64_t* __restrict__ done,
+                                                           float* __restrict__ ep_ret, int32_t* __restrict__ ep_len,
+                                                           float* __restrict__ ret_out, int32_t* __restrict__ len_out,
+                                                           int n, int tag, int env_id0,
+                                                           ouz_episode_record* __restrict__ records, uint32_t capacity,
+                                                           uint32_t* __restrict__ count) {
+#pragma clang fp contract(off)
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  bool fin = false;
+  float r = 0.0f;
+  int32_t l = 0;
+  if (i < n) {
+    const int64_t keep = 1 - done[i];            // torch: 1 - done stays int64
+    r = ep_ret[i] + rew[i];
+    l = ep_len[i] + 1;
+    ret_out[i] = r;
+    len_out[i] = l;
+    ep_ret[i] = r * (float)keep;                 // f32 *= int64 promotes the mask to f32
+    ep_len[i] = (int32_t)((int64_t)l * keep);    // i32 *= int64 computes in int64 and casts back
+    fin = keep != 1;
+  }
+  if (records == nullptr) return;                // launch-uniform
+  const unsigned long long mask = __ballot(fin);
+  if (mask == 0ull) return;                      // wave-uniform
+  const int lane = (int)(threadIdx.x & 63u);
+  const int leader = __ffsll((long long)mask) - 1;
+  uint32_t base = 0u;
+  if (lane == leader) base = atomicAdd(count, (uint32_t)__popcll(mask));
+  base = (uint32_t)__shfl((int)base, leader);
+  if (fin) {
+    const uint32_t slot = base + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
+    if (slot < capacity)
+      *reinterpret_cast<int4*>(records + slot) = make_int4(tag, env_id0 + i, __float_as_int(r), l);
   }
 }
 
@@ -952,6 +1001,23 @@ int ouz_pomdp_obs(const float* in, float* out, int32_t rows, int32_t dim, int32_
   hipLaunchKernelGGL(pomdp_obs_kernel, dim3(grid(rows, 256)), dim3(256), 0, (hipStream_t)stream, in, out, rows, dim,
                      zero, noise, lo, hi, seed, (uint32_t)row_offset, call);
   return launch_status("pomdp_obs_kernel");
+}
+
+int ouz_episode_step(const float* rew, const int64_t* done, float* ep_ret, int32_t* ep_len, float* ret_out,
+                     int32_t* len_out, int32_t n, int32_t tag, int32_t env_id0, ouz_episode_record* records,
+                     int32_t capacity, uint32_t* count, void* stream) {
+  if (n <= 0) return set_error(OUZ_ERR_INVALID, "ouz_episode_step: n must be > 0");
+  if (!rew || !done || !ep_ret || !ep_len || !ret_out || !len_out)
+    return set_error(OUZ_ERR_INVALID, "ouz_episode_step: null statistics buffer");
+  if (records) {
+    if (!count) return set_error(OUZ_ERR_INVALID, "ouz_episode_step: records without count");
+    if (capacity <= 0) return set_error(OUZ_ERR_INVALID, "ouz_episode_step: capacity must be > 0");
+    if ((reinterpret_cast<uintptr_t>(records) & 15u) != 0)
+      return set_error(OUZ_ERR_INVALID, "ouz_episode_step: records must be 16-byte aligned");
+  }
+  hipLaunchKernelGGL(episode_step_kernel, dim3(grid(n, 256)), dim3(256), 0, (hipStream_t)stream, rew, done, ep_ret,
+                     ep_len, ret_out, len_out, n, tag, env_id0, records, records ? (uint32_t)capacity : 0u, count);
+  return launch_status("episode_step_kernel");
 }
 
 int ouz_lstm_cell_fwd(const float* gates, const float* c_prev_m, const float* keep_next, float* act, float* c_out,

@@ -91,7 +91,7 @@ def gae(rewards, values, dones, next_value, next_done, gamma=0.99, lam=0.95):
 
 class PPOLearner:
     def __init__(self, observation_space, action_space, num_envs, device, recurrent=True, rollout_steps=16,
-                 lr=0.0026, num_minibatches=2, update_epochs=4, tuned_gemms=True):
+                 lr=0.0026, num_minibatches=2, update_epochs=4, tuned_gemms=True, rpo_alpha=None):
         self.obs_dim = observation_space
         self.act_dim = action_space
         self.num_envs = num_envs
@@ -115,8 +115,12 @@ class PPOLearner:
             raise ValueError("num_envs must divide into the minibatches")   # agent.py:72
         if tuned_gemms:
             enable_tuned_gemms(self.device)   # per-shape GEMM solutions (gemm_tuning.py); OUZ_TUNABLEOP=0: off
-        self.actor = (LSTMActor(observation_space, action_space) if recurrent
-                      else MLPActor(observation_space, action_space)).to(self.device)
+        # rpo_alpha None: each actor's own default (0.5 recurrent, RPO-LSTM/model.py:61; 0 for the MLP, PPO/model.py);
+        # a value selects the RPO / PPO-LSTM variants (learners/variants.py).  With 0 the update draws no noise.
+        alpha_kw = {} if rpo_alpha is None else {"rpo_alpha": float(rpo_alpha)}
+        self.actor = (LSTMActor(observation_space, action_space, **alpha_kw) if recurrent
+                      else MLPActor(observation_space, action_space, **alpha_kw)).to(self.device)
+        self.rpo_alpha = self.actor.rpo_alpha
         self.critic = Critic(observation_space).to(self.device)
         broadcast_params(self.actor)
         broadcast_params(self.critic)
