@@ -2,30 +2,30 @@
 
     python -m ouzelum_amd.learners.train --env Landing --num_envs 4096 --POMDP flicker --pomdp_prob 0.1
 
-Same loop as the reference: T-step rollout with the LSTM carry reset on done, the
-actor acting on the clean observations and training on the learner-side POMDP ones
-(App. B item 10; ``--rollout_obs pomdp`` gives the RPO-LSTM_Critic variant), one
-PPO update per rollout, best/final checkpoints under the reference's file names.
+The reference's loop, once for every learner: a T-step rollout with the LSTM carry reset on done (``Rollout``, which
+``scripts/bench_learner.py`` times too), one PPO update per rollout, best/final checkpoints under the reference's file
+names.  What differs between learners is a row of ``variants.py``: the actor (MLP / LSTM), ``rpo_alpha`` in the
+update, which observation the policy acts on and the critic values, and the names of the run directory, the final
+and the best checkpoint.  ``--learner NAME`` picks one of the reference's seven by its directory name (``PPO``,
+``RPO``, ``PPO-LSTM``, ``RPO-LSTM_Critic``, ``PPO_Critic``, ``RPO_Critic``, ``RPO-LSTM``), so curves and checkpoints
+lie over the reference's; ``--algo`` / ``--rollout_obs`` (the older flags, not to be combined with ``--learner``) make
+a row of their own (``variants.legacy_variant``): the actor acts on the clean observations and trains on the
+learner-side POMDP ones (App. B item 10), ``--rollout_obs pomdp`` gives the RPO-LSTM_Critic routing.
+
 The reference's TensorBoard scalars (PPO/main.py:101-109: ``charts/episodic_return``, ``charts/episodic_length``,
 ``average/average_reward``) go to a TensorBoard event file in ``<logdir>/<run>/`` (the reference's
-``SummaryWriter("../runs/<run>")``; written by ``tbevents.py``, tensorboard itself is not installed), one point per
-rollout: the mean return / length of the episodes that finished in it, where the reference logs the episodes that
-end in the rollout's first three steps one by one.  Every logged column also goes to ``<logdir>/<run>.csv``.  Episode
-statistics are the env's in-kernel [sum, count] (``ouz_episode_stats``), all-reduced
-over RCCL when launched with torchrun (one process per GPU, env ids sharded).
+``SummaryWriter("../runs/<run>")``; written by ``tbevents.py``, tensorboard itself is not installed), by default one
+point per rollout: the mean return / length of the episodes that finished in it, from the env's in-kernel
+[sum, count] (``ouz_episode_stats``), all-reduced over RCCL when launched with torchrun (one process per GPU, env ids
+sharded).  Every logged column also goes to ``<logdir>/<run>.csv``.
 
-``--learner NAME`` runs one of the reference's seven learners by its directory name (``PPO``, ``RPO``, ``PPO-LSTM``,
-``RPO-LSTM_Critic``, ``PPO_Critic``, ``RPO_Critic``, ``RPO-LSTM``; the table is ``variants.py``): it decides the actor
-(MLP / LSTM), ``rpo_alpha`` in the update, which observation the policy acts on and the critic values, and the names
-of the run directory, the final and the best checkpoint, so curves and checkpoints lie over the reference's.  It
-cannot be combined with ``--algo`` / ``--rollout_obs``, which keep their own (older) loop unchanged.  On this path
-the per-step episode bookkeeping is one ``ouz_episode_step`` launch (``wrappers.EpisodeRecorder``), and
-``--episode_log per_episode`` writes the reference's points: one ``charts/episodic_return`` /
+The per-step episode bookkeeping is one ``ouz_episode_step`` launch (``wrappers.EpisodeRecorder``), and
+``--learner NAME --episode_log per_episode`` writes the reference's points: one ``charts/episodic_return`` /
 ``charts/episodic_length`` pair per episode that ends in rollout steps 0-2, env ids ascending, at that step's
 ``global_step`` (PPO/main.py:98-103).  The rollout loop reads nothing back for them: the kernel appends the records
 on the device, and the host reads the count and ``records[:count]`` once per rollout, after the synchronize the
-loop already has.  ``--play --learner NAME`` runs NAME's networks from ``--checkpoint`` on the observations NAME's
-rollout feeds its policy and logs ``reward/play``.
+loop already has.  ``--play`` runs the row's networks from ``--checkpoint``; with ``--learner NAME`` on the
+observations NAME's rollout feeds its policy, logging ``reward/play``.
 """
 import argparse
 import csv
@@ -41,9 +41,11 @@ from ..vec_task import make
 from .fused import store
 from .ppo import PPOLearner
 from .tbevents import EventWriter
-from .variants import LEARNERS, VARIANTS, names, single_stream
-from .wrappers import (RECORD_DTYPE, EpisodeRecorder, ExtractObsWrapper, POMDPWrapper, RecordEpisodeStatisticsTorch,
-                       merge_records)
+from .variants import LEARNERS, VARIANTS, legacy_variant, names, single_stream
+from .wrappers import RECORD_DTYPE, EpisodeRecorder, ExtractObsWrapper, POMDPWrapper, merge_records
+
+COLUMNS = ("global_step", "average_reward", "episodes", "episodic_return", "episodic_length", "pg_loss", "v_loss",
+           "approx_kl", "clipfrac", "env_steps_per_s")
 
 
 def parse_args(argv=None):
@@ -82,6 +84,11 @@ def parse_args(argv=None):
     return args
 
 
+def variant_of(args):
+    """The table row the flags select: ``--learner``'s, or the one ``--algo`` / ``--rollout_obs`` describe."""
+    return VARIANTS[args.learner] if args.learner is not None else legacy_variant(args.algo, args.rollout_obs)
+
+
 def write_episode_points(tb, records, g0, step_envs):
     """The reference's per-episode points (PPO/main.py:98-103) from a rollout's records sorted by (tag, env id):
     ``charts/episodic_return`` then ``charts/episodic_length`` per record, at the ``global_step`` after the
@@ -109,15 +116,86 @@ def gather_records(rec, world):
     return merged
 
 
-def train_learner(args, on_rollout=None):
-    """``train`` for ``--learner NAME``: the same loop with NAME's routing and names (variants.py), the episode
-    bookkeeping as one launch per step, and optionally the reference's per-episode points.  ``on_rollout(dict)``, if
-    given, is called once per rollout (after the update and the synchronize) with the rollout's tensors: ``obs`` and
-    ``pomdps`` storage (``pomdps`` None for the single-stream learners), the bootstrap ``next_obs``, ``acted_on``
-    (T, N, d: what the policy was given at each step), ``dones`` (T, N: ``next_done`` after each step),
-    ``r`` / ``l`` (T, N: info["r"] / info["l"] after each step), ``global_step_before`` and ``stats``."""
-    v = VARIANTS[args.learner]
-    single = single_stream(v)
+class Rollout:
+    """The rollout of every learner: the (T, N) storage, the state carried from one rollout to the next, and the
+    step loop in the routing of the row ``v`` (variants.py).  ``envs`` hands out observation tensors
+    (``ExtractObsWrapper``), with or without an ``EpisodeRecorder`` around it.  Resets ``envs``: the first
+    observation of a run is the clean one in every routing (main.py:80-82).  ``watch=True`` (needs the recorder)
+    also keeps in ``seen`` what no learner stores: ``acted_on`` (T, N, d: what the policy was given at each step),
+    ``dones`` (T, N: ``next_done`` after each step) and ``r`` / ``l`` (T, N: info["r"] / info["l"] after each step)."""
+
+    def __init__(self, envs, pomdp_w, agent, v, T, watch=False):
+        self.envs, self.pomdp_w, self.agent, self.v, self.T = envs, pomdp_w, agent, v, T
+        self.single = single_stream(v)
+        N, device = agent.num_envs, agent.device
+        obs_shape = envs.observation_space.shape
+        self.obs = torch.zeros((T, N) + obs_shape, device=device)
+        self.pomdps = None if self.single else torch.zeros((T, N) + obs_shape, device=device)
+        self.actions = torch.zeros((T, N) + envs.action_space.shape, device=device)
+        self.logprobs = torch.zeros((T, N), device=device)
+        self.rewards = torch.zeros((T, N), device=device)
+        self.dones = torch.zeros((T, N), device=device)
+        self.seen = None
+        if watch:
+            self.seen = {"acted_on": torch.zeros((T, N) + obs_shape, device=device),
+                         "dones": torch.zeros((T, N), dtype=torch.int64, device=device),
+                         "r": torch.zeros((T, N), device=device),
+                         "l": torch.zeros((T, N), dtype=torch.int32, device=device)}
+        self.next_obs = envs.reset()
+        self.pomdp = self.next_obs.clone()
+        if self.single:
+            self.next_obs = self.pomdp        # a tensor of its own: the env overwrites its observation buffer in place
+        self.next_done = torch.zeros(N, device=device)
+        self.lstm_state = agent.initial_state()
+        self.init_state = None
+
+    def collect(self, per_episode=False):
+        """T steps on from where the last call stopped.  ``per_episode`` (needs the recorder) appends the records of
+        the episodes that end in steps 0-2 (PPO/main.py:98: ``if 0 <= step <= 2``)."""
+        envs, pomdp_w, agent, seen, single = self.envs, self.pomdp_w, self.agent, self.seen, self.single
+        obs, pomdps, actions, logprobs, rewards, dones = (self.obs, self.pomdps, self.actions, self.logprobs,
+                                                          self.rewards, self.dones)
+        acts_on_pomdp = self.v.acts_on == "pomdp"
+        next_obs, pomdp, next_done, lstm_state = self.next_obs, self.pomdp, self.next_done, self.lstm_state
+        self.init_state = (lstm_state[0].clone(), lstm_state[1].clone()) if lstm_state is not None else None
+        if per_episode:
+            envs.begin_rollout()
+        for step in range(self.T):
+            if single:
+                store((obs[step], dones[step]), (next_obs, next_done))
+                act_in = next_obs
+            else:
+                store((pomdps[step], obs[step], dones[step]), (pomdp, next_obs, next_done))  # one multi-tensor copy
+                act_in = pomdp if acts_on_pomdp else next_obs
+            if seen is not None:
+                seen["acted_on"][step].copy_(act_in)
+            # alias=True: the policy graph's output buffers (actions[step] / logprobs[step] copy them before the next
+            # replay); alias=False adds 5 clones per step
+            action, logprob, _, lstm_state = agent.act(act_in, lstm_state, next_done, alias=True)
+            store((actions[step], logprobs[step]), (action, logprob))
+            if per_episode and step <= 2:
+                envs.record(step)
+            next_obs, rewards[step], next_done, info = envs.step(action)
+            if single:
+                next_obs = pomdp_w.observation(next_obs)     # PPO/main.py:96
+            else:
+                pomdp = pomdp_w.observation(next_obs)        # RPO-LSTM/main.py:103
+            if seen is not None:
+                store((seen["dones"][step], seen["r"][step], seen["l"][step]), (next_done, info["r"], info["l"]))
+        self.next_obs, self.pomdp, self.next_done, self.lstm_state = next_obs, pomdp, next_done, lstm_state
+
+    def update(self):
+        """One PPO update on the rollout just collected; the actor trains on the POMDP stream."""
+        return self.agent.train(self.obs, self.obs if self.single else self.pomdps, self.actions, self.next_obs,
+                                self.next_done, self.init_state, self.logprobs, self.rewards, self.dones)
+
+
+def train(args, on_rollout=None):
+    """``on_rollout(dict)``, if given, is called once per rollout (after the update and the synchronize) with the
+    rollout's tensors: ``obs`` and ``pomdps`` storage (``pomdps`` None for the single-stream learners), the bootstrap
+    ``next_obs``, ``Rollout.seen``'s ``acted_on`` / ``dones`` / ``r`` / ``l``, ``global_step_before``, ``stats`` and
+    the per-episode ``records`` (None with ``--episode_log rollout_mean``)."""
+    v = variant_of(args)
     per_episode = args.episode_log == "per_episode"
     rank, world, local = init_from_env()
     device = torch.device("cuda", local)
@@ -133,19 +211,8 @@ def train_learner(args, on_rollout=None):
     pomdp_w = POMDPWrapper(args.POMDP, args.pomdp_prob, seed=args.seed + 1, row_offset=off)
     agent = PPOLearner(base.observation_space, base.action_space, N, device, recurrent=v.recurrent,
                        rollout_steps=T, rpo_alpha=v.rpo_alpha)
-    name, best = names(args.learner, args.POMDP, args.pomdp_prob)
-
-    obs_shape = base.observation_space.shape
-    obs = torch.zeros((T, N) + obs_shape, device=device)
-    pomdps = None if single else torch.zeros((T, N) + obs_shape, device=device)
-    actions = torch.zeros((T, N) + base.action_space.shape, device=device)
-    logprobs = torch.zeros((T, N), device=device)
-    rewards = torch.zeros((T, N), device=device)
-    dones = torch.zeros((T, N), device=device)
-    if on_rollout is not None:
-        seen = {"acted_on": torch.zeros((T, N) + obs_shape, device=device),
-                "dones": torch.zeros((T, N), dtype=torch.int64, device=device),
-                "r": torch.zeros((T, N), device=device), "l": torch.zeros((T, N), dtype=torch.int32, device=device)}
+    name, best = names(v, args.POMDP, args.pomdp_prob)
+    ro = Rollout(envs, pomdp_w, agent, v, T, watch=on_rollout is not None)
 
     writer = tb = None
     if rank == 0:
@@ -153,50 +220,20 @@ def train_learner(args, on_rollout=None):
         tb = EventWriter(os.path.join(args.logdir, name))
         fh = open(os.path.join(args.logdir, name + ".csv"), "w", newline="")
         writer = csv.writer(fh)
-        writer.writerow(["global_step", "average_reward", "episodes", "episodic_return", "episodic_length",
-                         "pg_loss", "v_loss", "approx_kl", "clipfrac", "env_steps_per_s"])
+        writer.writerow(COLUMNS)
 
     global_step = 0
     max_reward = -float("inf")
-    next_obs = envs.reset()
-    pomdp = next_obs.clone()              # the first observation of a run is the clean one (main.py:80-82)
-    if single:
-        next_obs = pomdp                  # a tensor of its own: the env overwrites its observation buffer in place
-    next_done = torch.zeros(N, device=device)
-    lstm_state = agent.initial_state()
     history = []
     t_start = time.perf_counter()
     while global_step < args.total_steps:
         t0 = time.perf_counter()
         g0 = global_step
-        init_state = (lstm_state[0].clone(), lstm_state[1].clone()) if lstm_state is not None else None
-        if per_episode:
-            envs.begin_rollout()
-        for step in range(T):
-            global_step += N * world
-            if single:
-                store((obs[step], dones[step]), (next_obs, next_done))
-                act_in = next_obs
-            else:
-                store((pomdps[step], obs[step], dones[step]), (pomdp, next_obs, next_done))
-                act_in = pomdp if v.acts_on == "pomdp" else next_obs
-            if on_rollout is not None:
-                seen["acted_on"][step].copy_(act_in)
-            action, logprob, _, lstm_state = agent.act(act_in, lstm_state, next_done, alias=True)
-            store((actions[step], logprobs[step]), (action, logprob))
-            if per_episode and step <= 2:         # PPO/main.py:98: if 0 <= step <= 2
-                envs.record(step)
-            next_obs, rewards[step], next_done, info = envs.step(action)
-            if single:
-                next_obs = pomdp_w.observation(next_obs)     # PPO/main.py:96
-            else:
-                pomdp = pomdp_w.observation(next_obs)        # RPO-LSTM/main.py:103
-            if on_rollout is not None:
-                store((seen["dones"][step], seen["r"][step], seen["l"][step]), (next_done, info["r"], info["l"]))
-        stats = agent.train(obs, obs if single else pomdps, actions, next_obs, next_done, init_state, logprobs,
-                            rewards, dones)
+        ro.collect(per_episode)
+        global_step += T * N * world
+        stats = ro.update()
         ep = base.episode_stats()
-        mean_rew = rewards.mean()
+        mean_rew = ro.rewards.mean()
         merged = None
         if world > 1:
             dist.all_reduce(ep)
@@ -205,7 +242,7 @@ def train_learner(args, on_rollout=None):
             if per_episode:
                 merged = gather_records(envs, world)
         torch.cuda.synchronize(device)
-        base.check_health()
+        base.check_health()   # raises if a fused rollout's split-wave wait gave up (never on the per-step path)
         records = None
         if per_episode:   # the rollout's only host reads for the points: the count, then records[:count]
             records = merged() if merged is not None else envs.drain()
@@ -216,12 +253,10 @@ def train_learner(args, on_rollout=None):
                **{k: float(x) for k, x in stats.items()}, "env_steps_per_s": sps}
         history.append(row)
         if on_rollout is not None:
-            on_rollout({"obs": obs, "pomdps": pomdps, "next_obs": next_obs, **seen, "global_step_before": g0,
-                        "stats": stats, "records": records})
+            on_rollout({"obs": ro.obs, "pomdps": ro.pomdps, "next_obs": ro.next_obs, **ro.seen,
+                        "global_step_before": g0, "stats": stats, "records": records})
         if rank == 0:
-            writer.writerow([row[k] for k in ("global_step", "average_reward", "episodes", "episodic_return",
-                                              "episodic_length", "pg_loss", "v_loss", "approx_kl", "clipfrac",
-                                              "env_steps_per_s")])
+            writer.writerow([row[k] for k in COLUMNS])
             if per_episode:
                 write_episode_points(tb, records, g0, N * world)
             elif row["episodes"] > 0:
@@ -246,137 +281,17 @@ def train_learner(args, on_rollout=None):
             "env_steps_per_s": global_step / elapsed, "run": name, "best": best}
 
 
-def train(args, on_rollout=None):
-    if getattr(args, "learner", None) is not None:
-        return train_learner(args, on_rollout)
-    if on_rollout is not None:
-        raise ValueError("on_rollout is a hook of the --learner loop")
-    rank, world, local = init_from_env()
-    device = torch.device("cuda", local)
-    torch.cuda.set_device(device)
-    np.random.seed(args.seed + rank)
-    torch.manual_seed(args.seed + rank)
-    N, T = args.num_envs, args.rollout_steps
-    off, total = shard(N, rank, world)
-
-    base = make(seed=args.seed, task=args.env, num_envs=N, sim_device=str(device), rl_device=str(device),
-                graphics_device_id=-1, headless=True, env_id_offset=off, num_envs_total=total, track_episodes=True)
-    envs = RecordEpisodeStatisticsTorch(ExtractObsWrapper(base), device)
-    pomdp_w = POMDPWrapper(args.POMDP, args.pomdp_prob, seed=args.seed + 1, row_offset=off)
-    agent = PPOLearner(base.observation_space, base.action_space, N, device, recurrent=args.algo == "rpo_lstm",
-                       rollout_steps=T)
-    name = f"{'RPO_LSTM' if args.algo == 'rpo_lstm' else 'PPO'}_{args.POMDP}_{args.pomdp_prob}"
-
-    obs_shape = base.observation_space.shape
-    obs = torch.zeros((T, N) + obs_shape, device=device)
-    pomdps = torch.zeros((T, N) + obs_shape, device=device)
-    actions = torch.zeros((T, N) + base.action_space.shape, device=device)
-    logprobs = torch.zeros((T, N), device=device)
-    rewards = torch.zeros((T, N), device=device)
-    dones = torch.zeros((T, N), device=device)
-
-    writer = tb = None
-    if rank == 0:
-        os.makedirs(args.logdir, exist_ok=True)
-        tb = EventWriter(os.path.join(args.logdir, name))
-        fh = open(os.path.join(args.logdir, name + ".csv"), "w", newline="")
-        writer = csv.writer(fh)
-        writer.writerow(["global_step", "average_reward", "episodes", "episodic_return", "episodic_length",
-                         "pg_loss", "v_loss", "approx_kl", "clipfrac", "env_steps_per_s"])
-
-    global_step = 0
-    max_reward = -float("inf")
-    next_obs = envs.reset()
-    pomdp = next_obs.clone()
-    next_done = torch.zeros(N, device=device)
-    lstm_state = agent.initial_state()
-    history = []
-    t_start = time.perf_counter()
-    while global_step < args.total_steps:
-        t0 = time.perf_counter()
-        init_state = (lstm_state[0].clone(), lstm_state[1].clone()) if lstm_state is not None else None
-        for step in range(T):
-            global_step += N * world
-            store((pomdps[step], obs[step], dones[step]), (pomdp, next_obs, next_done))
-            act_in = pomdp if args.rollout_obs == "pomdp" else next_obs
-            action, logprob, _, lstm_state = agent.act(act_in, lstm_state, next_done, alias=True)
-            store((actions[step], logprobs[step]), (action, logprob))
-            next_obs, rewards[step], next_done, info = envs.step(action)
-            pomdp = pomdp_w.observation(next_obs)
-        stats = agent.train(obs, pomdps, actions, next_obs, next_done, init_state, logprobs, rewards, dones)
-        ep = base.episode_stats()
-        mean_rew = rewards.mean()
-        if world > 1:
-            dist.all_reduce(ep)
-            dist.all_reduce(mean_rew)
-            mean_rew /= world
-        torch.cuda.synchronize(device)
-        base.check_health()   # raises if a fused rollout's split-wave wait gave up (never on the per-step path)
-        sps = N * world * T / (time.perf_counter() - t0)
-        row = {"global_step": global_step, "average_reward": float(mean_rew), "episodes": int(ep[1]),
-               "episodic_return": float(ep[0] / ep[1]) if float(ep[1]) > 0 else float("nan"),
-               "episodic_length": float(ep[2] / ep[1]) if float(ep[1]) > 0 else float("nan"),
-               **{k: float(v) for k, v in stats.items()}, "env_steps_per_s": sps}
-        history.append(row)
-        if rank == 0:
-            writer.writerow([row[k] for k in ("global_step", "average_reward", "episodes", "episodic_return",
-                                              "episodic_length", "pg_loss", "v_loss", "approx_kl", "clipfrac",
-                                              "env_steps_per_s")])
-            if row["episodes"] > 0:
-                tb.add_scalar("charts/episodic_return", row["episodic_return"], global_step)
-                tb.add_scalar("charts/episodic_length", row["episodic_length"], global_step)
-            tb.add_scalar("average/average_reward", row["average_reward"], global_step)
-            tb.flush()
-            if not args.quiet:
-                print(f"Step: {global_step}, Average rewards {row['average_reward']:.4f}, "
-                      f"{sps / 1e6:.2f} M env-steps/s", flush=True)
-            if not args.no_checkpoints and row["average_reward"] > max_reward:
-                max_reward = row["average_reward"]
-                os.makedirs(args.checkpoint_dir, exist_ok=True)
-                agent.save(os.path.join(args.checkpoint_dir, f"best_reward_{args.POMDP}_{args.pomdp_prob}"))
-    if rank == 0:
-        if not args.no_checkpoints:
-            agent.save(os.path.join(args.checkpoint_dir, name))
-        fh.close()
-        tb.close()
-    elapsed = time.perf_counter() - t_start
-    return {"history": history, "agent": agent, "env": base, "elapsed": elapsed, "events": tb.path if tb else None,
-            "env_steps_per_s": global_step / elapsed}
-
-
 @torch.no_grad()
 def play(args):
-    """RPO-LSTM/play.py:25-80: load a checkpoint and run the policy, printing the mean reward."""
-    device = torch.device("cuda", 0)
-    N = args.num_envs
-    base = make(seed=args.seed, task=args.env, num_envs=N, sim_device=str(device), rl_device=str(device),
-                track_episodes=True)
-    env = ExtractObsWrapper(base)
-    agent = PPOLearner(base.observation_space, base.action_space, N, device, recurrent=args.algo == "rpo_lstm",
-                       rollout_steps=args.rollout_steps, tuned_gemms=False)   # inference only
-    if args.checkpoint:
-        agent.load(args.checkpoint)
-    next_obs = env.reset()
-    next_done = torch.zeros(N, device=device)
-    lstm = agent.initial_state()
-    rewards = []
-    for _ in range(max(1, args.total_steps // N)):
-        action, _, _, lstm = agent.act(next_obs, lstm, next_done)
-        next_obs, rew, next_done, _ = env.step(action)
-        rewards.append(rew.mean())
-        if not args.quiet:
-            print(f"Average rewards {float(rewards[-1]):.4f}")
-    return {"mean_reward": float(torch.stack(rewards).mean()), "episode_stats": base.episode_stats().tolist()}
-
-
-@torch.no_grad()
-def play_learner(args):
-    """``--play --learner NAME``: NAME's networks (variants.py) from ``--checkpoint``, fed what NAME's rollout feeds
-    its policy: the POMDP observation for the five learners that act on it, the clean one for PPO-LSTM and RPO-LSTM;
-    the first observation is the clean reset, as in training.  Logs the reference's ``reward/play`` scalar (the
-    step's mean reward at ``global_step``, RPO-LSTM_Critic/play.py:78-94) to an event file under ``--logdir``.
-    (The reference's RPO/play.py is a stale copy that skips the corruption; this follows the table.)"""
-    v = VARIANTS[args.learner]
+    """RPO-LSTM/play.py:25-80: load a checkpoint and run the row's policy, printing the mean reward.  With
+    ``--learner NAME`` the policy is fed what NAME's rollout feeds it: the POMDP observation for the five learners
+    that act on it, the clean one for PPO-LSTM and RPO-LSTM; the first observation is the clean reset, as in
+    training; and the reference's ``reward/play`` scalar (the step's mean reward at ``global_step``,
+    RPO-LSTM_Critic/play.py:78-94) goes to an event file under ``--logdir``.  (The reference's RPO/play.py is a stale
+    copy that skips the corruption; this follows the table.)  ``--algo`` plays on the clean observation whatever
+    ``--rollout_obs`` says, and writes no event file."""
+    v = variant_of(args)
+    by_name = args.learner is not None
     device = torch.device("cuda", 0)
     N = args.num_envs
     base = make(seed=args.seed, task=args.env, num_envs=N, sim_device=str(device), rl_device=str(device),
@@ -387,8 +302,9 @@ def play_learner(args):
     if args.checkpoint:
         agent.load(args.checkpoint)
     pomdp_w = POMDPWrapper(args.POMDP, args.pomdp_prob, seed=args.seed + 1)
-    name, _ = names(args.learner, args.POMDP, args.pomdp_prob)
-    tb = EventWriter(os.path.join(args.logdir, name + "_play"))
+    tb = None
+    if by_name:
+        tb = EventWriter(os.path.join(args.logdir, names(v, args.POMDP, args.pomdp_prob)[0] + "_play"))
     act_in = env.reset().clone()
     next_done = torch.zeros(N, device=device)
     lstm = agent.initial_state()
@@ -396,21 +312,25 @@ def play_learner(args):
     for _ in range(max(1, args.total_steps // N)):
         global_step += N
         action, _, _, lstm = agent.act(act_in, lstm, next_done)
-        next_obs, rew, next_done, _ = env.step(action)
-        act_in = pomdp_w.observation(next_obs) if v.acts_on == "pomdp" else next_obs
+        act_in, rew, next_done, _ = env.step(action)
+        if by_name and v.acts_on == "pomdp":
+            act_in = pomdp_w.observation(act_in)
         rewards.append(rew.mean())
-        tb.add_scalar("reward/play", float(rewards[-1]), global_step)
+        if tb is not None:
+            tb.add_scalar("reward/play", float(rewards[-1]), global_step)
         if not args.quiet:
-            print(f"Step: {global_step}, Average rewards {float(rewards[-1]):.4f}")
-    tb.close()
-    return {"mean_reward": float(torch.stack(rewards).mean()), "episode_stats": base.episode_stats().tolist(),
-            "events": tb.path}
+            print((f"Step: {global_step}, " if by_name else "") + f"Average rewards {float(rewards[-1]):.4f}")
+    out = {"mean_reward": float(torch.stack(rewards).mean()), "episode_stats": base.episode_stats().tolist()}
+    if tb is not None:
+        tb.close()
+        out["events"] = tb.path
+    return out
 
 
 def main(argv=None):
     args = parse_args(argv)
     if args.play:
-        return play_learner(args) if args.learner is not None else play(args)
+        return play(args)
     out = train(args)
     if dist.is_initialized():
         dist.destroy_process_group()

@@ -48,9 +48,19 @@ GRID = (("flicker", (0.1, 0.2, 0.3, 0.4, 0.5)),
         ("flickering_and_random_noise", (0.05, 0.1, 0.15, 0.2, 0.25)))
 
 
+def legacy_variant(algo, rollout_obs):
+    """``train.py --algo {rpo_lstm, ppo} --rollout_obs {clean, pomdp}`` as a row: each actor's default ``rpo_alpha``
+    (None), the critic on the clean observations with the separate ``pomdps`` storage, the names those flags have
+    always written.  Not one of the reference's seven (``--algo ppo --rollout_obs clean`` matches none of them)."""
+    recurrent = algo == "rpo_lstm"
+    return Variant(recurrent, None, rollout_obs, "clean", ("RPO_LSTM" if recurrent else "PPO") + "_{P}_{p}",
+                   "best_reward_{P}_{p}")
+
+
 def names(learner, pomdp, prob):
-    """(run and final-checkpoint name, best-checkpoint name) of ``learner`` at this POMDP setting."""
-    v = VARIANTS[learner]
+    """(run and final-checkpoint name, best-checkpoint name) of ``learner`` (a key of ``VARIANTS``, or a row) at
+    this POMDP setting."""
+    v = VARIANTS[learner] if isinstance(learner, str) else learner
     return v.run.format(P=pomdp, p=prob), v.best.format(P=pomdp, p=prob)
 
 

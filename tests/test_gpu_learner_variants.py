@@ -1,5 +1,6 @@
-"""``train --learner NAME`` on the MI355X for each of the reference's seven learners: the observation routing of
-the table (ouzelum_amd/learners/variants.py), the run / checkpoint names, play, and the per-episode points.
+"""``train --learner NAME`` on the MI355X for each of the reference's seven learners, and the four combinations of the
+older ``--algo`` / ``--rollout_obs`` flags: the observation routing of the row (ouzelum_amd/learners/variants.py), the
+run / checkpoint names, play, and the per-episode points.
 
 The routing is read off with ``--POMDP flicker --pomdp_prob 1.0``: the flicker coin ``unit_f32(...) <= p`` then always
 holds, so every corrupted observation is all zero, while a clean observation never is (the quaternion's w is near
@@ -13,16 +14,22 @@ import torch
 
 from ouzelum_amd.learners import train as T
 from ouzelum_amd.learners.tbevents import read_scalars
-from ouzelum_amd.learners.variants import LEARNERS, VARIANTS, names
+from ouzelum_amd.learners.variants import LEARNERS, VARIANTS, legacy_variant, names
 
 pytestmark = pytest.mark.gpu
 
 
-@pytest.mark.parametrize("name", LEARNERS)
+LEGACY = [(algo, rollout_obs) for algo in ("rpo_lstm", "ppo") for rollout_obs in ("clean", "pomdp")]
+
+
+@pytest.mark.parametrize("name", [*LEARNERS, *(pytest.param(f, id="-".join(f)) for f in LEGACY)])
 def test_learner_routing_names_and_play(tmp_path, name):
-    v = VARIANTS[name]
+    """``name``: one of the seven learners, or an (--algo, --rollout_obs) pair of the older flags."""
+    legacy = not isinstance(name, str)
+    v = legacy_variant(*name) if legacy else VARIANTS[name]
+    flags = ["--algo", name[0], "--rollout_obs", name[1]] if legacy else ["--learner", name]
     n, rollouts = 64, 3
-    args = T.parse_args(["--learner", name, "--env", "Ouzelum", "--num_envs", str(n), "--total_steps",
+    args = T.parse_args([*flags, "--env", "Ouzelum", "--num_envs", str(n), "--total_steps",
                          str(n * 16 * rollouts), "--POMDP", "flicker", "--pomdp_prob", "1.0", "--logdir",
                          str(tmp_path / "runs"), "--checkpoint_dir", str(tmp_path / "ck"), "--quiet"])
     seen = []
@@ -50,16 +57,25 @@ def test_learner_routing_names_and_play(tmp_path, name):
     for row in out["history"]:
         for k in ("average_reward", "pg_loss", "v_loss", "approx_kl"):
             assert np.isfinite(row[k]), (k, row)
-    assert out["agent"].recurrent is v.recurrent and out["agent"].actor.rpo_alpha == v.rpo_alpha
-    run, best = names(name, "flicker", 1.0)
+    alpha = v.rpo_alpha if v.rpo_alpha is not None else (0.5 if v.recurrent else 0.0)    # None: the actor's own
+    assert out["agent"].recurrent is v.recurrent and out["agent"].actor.rpo_alpha == alpha
+    run, best = names(v, "flicker", 1.0)
+    if legacy:
+        assert (run, best) == (("RPO_LSTM" if name[0] == "rpo_lstm" else "PPO") + "_flicker_1.0",
+                               "best_reward_flicker_1.0")
+    assert (out["run"], out["best"]) == (run, best)
     assert os.path.dirname(out["events"]) == str(tmp_path / "runs" / run)
     assert (tmp_path / "runs" / f"{run}.csv").exists()
     for suffix in ("_actor", "_critic", "_actor_optimizer", "_critic_optimizer"):
         assert (tmp_path / "ck" / (run + suffix)).exists() and (tmp_path / "ck" / (best + suffix)).exists()
-    res = T.main(["--play", "--learner", name, "--env", "Ouzelum", "--num_envs", str(n), "--total_steps", str(n * 5),
+    before = sorted(str(p) for p in (tmp_path / "runs").rglob("*"))
+    res = T.main(["--play", *flags, "--env", "Ouzelum", "--num_envs", str(n), "--total_steps", str(n * 5),
                   "--POMDP", "flicker", "--pomdp_prob", "1.0", "--checkpoint", str(tmp_path / "ck" / run),
                   "--logdir", str(tmp_path / "runs"), "--quiet"])
     assert np.isfinite(res["mean_reward"])
+    if legacy:                                    # the older flags' play writes no event file
+        assert "events" not in res and sorted(str(p) for p in (tmp_path / "runs").rglob("*")) == before
+        return
     pts, _ = read_scalars(res["events"])
     assert [(t, s) for t, s, _, _ in pts] == [("reward/play", n * (k + 1)) for k in range(5)]
     assert str(tmp_path / "runs") in res["events"]

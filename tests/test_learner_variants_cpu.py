@@ -44,6 +44,22 @@ def test_table_agrees_with_the_reference_fixture(fixture, name):
     assert list(V.LEARNERS) == fixture["order"] == NAMES
 
 
+@pytest.mark.parametrize("algo", ["rpo_lstm", "ppo"])
+@pytest.mark.parametrize("rollout_obs", ["clean", "pomdp"])
+def test_legacy_flags_are_a_row_outside_the_table(fixture, algo, rollout_obs):
+    v = V.legacy_variant(algo, rollout_obs)
+    assert isinstance(v, V.Variant)
+    assert v.recurrent is (algo == "rpo_lstm") and v.rpo_alpha is None      # None: the actor's own default
+    assert (v.acts_on, v.critic_on) == (rollout_obs, "clean") and not V.single_stream(v)
+    assert (v.run, v.best) == ("RPO_LSTM_{P}_{p}" if algo == "rpo_lstm" else "PPO_{P}_{p}", "best_reward_{P}_{p}")
+    assert V.names(v, "flicker", 0.1) == ("RPO_LSTM_flicker_0.1" if algo == "rpo_lstm" else "PPO_flicker_0.1",
+                                          "best_reward_flicker_0.1")
+    args = T.parse_args(["--algo", algo, "--rollout_obs", rollout_obs])
+    assert T.variant_of(args) == v and T.variant_of(T.parse_args(["--learner", "RPO"])) is V.VARIANTS["RPO"]
+    assert list(V.VARIANTS) == list(V.LEARNERS) == fixture["order"] == NAMES and len(V.VARIANTS) == 7
+    assert sum(len(ps) for _, ps in V.GRID) * len(V.LEARNERS) == len(fixture["grid"]) == 112
+
+
 def test_grid_is_the_reference_experiment_in_order(fixture, capsys):
     assert len(fixture["grid"]) == 112
     assert [list(x) for x in sweep.grid()] == fixture["grid"]
