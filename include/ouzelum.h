@@ -62,7 +62,7 @@
 extern "C" {
 #endif
 
-#define OUZ_ABI_VERSION 7  /* 2: trigger-class state layout of the estimator tasks (ouz_state_slots);
+#define OUZ_ABI_VERSION 8  /* 2: trigger-class state layout of the estimator tasks (ouz_state_slots);
                                3: 1344-id curriculum chunks of OUZ_TASK_MIXED with the class layout, ouz_env_slots;
                                4: physical domain randomisation (ouz_dr_physical, OUZ_I_RAND_STEP), DR noise
                                   frequency (ouz_dr_noise.frequency);
@@ -72,7 +72,9 @@ extern "C" {
                                   sequence kernels (ouz_lstm_seq_fwd / ouz_lstm_seq_bwd), clipped Adam
                                   (ouz_adam_clip_step), the small-K first layer (ouz_linear_tanh_small_k);
                                7: per-env episode statistics with the per-episode record append (ouz_episode_step,
-                                  ouz_episode_record) */
+                                  ouz_episode_record);
+                               8: the learner's bf16 GEMM mode (ouz_linear_tanh_small_k_bf16, ouz_tanh_bwd_bias_bf16,
+                                  ouz_adam_clip_step_shadow) */
 
 /* error codes */
 #define OUZ_OK 0
@@ -463,6 +465,11 @@ int ouz_lstm_seq_bwd(const float* act, const float* c_all, const float* cm, cons
  * [4, 1024], y 16-byte aligned.  tanh to ~1e-7 absolute (hardware exp2 / reciprocal). */
 int ouz_linear_tanh_small_k(const float* x, const float* w, const float* b, int32_t rows, int32_t K, int32_t cols,
                             float* y, void* stream);
+/* The same layer with a bf16 result (the learner's bf16 GEMM mode): x, W, b and the arithmetic are f32 as above, y
+ * [rows][cols] is bf16 (uint16_t bit patterns), rounded to nearest even once at the store.  Each thread stores eight
+ * consecutive outputs (16 bytes) where cols >= 8, four (8 bytes) at cols = 4. */
+int ouz_linear_tanh_small_k_bf16(const float* x, const float* w, const float* b, int32_t rows, int32_t K,
+                                 int32_t cols, uint16_t* y, void* stream);
 
 /* Gradient-norm clipping + Adam over one network's parameter tensors in two launches (RPO-LSTM/agent.py:124-134:
  * nn.utils.clip_grad_norm_(params, max_norm) then torch.optim.Adam.step(); torch/optim/adam.py single-tensor order).
@@ -482,6 +489,14 @@ typedef struct ouz_adam_table {
 } ouz_adam_table;
 int ouz_adam_clip_step(const ouz_adam_table* t, double lr, double beta1, double beta2, double eps, int64_t step,
                        double max_norm, float* workspace, void* stream);
+/* The same step (parameters and moments bit for bit, the same two launches) that also writes bf16 shadows of the
+ * updated parameters: shadow[i] [numel[i]] = the round-to-nearest-even bf16 of param[i] after the step (uint16_t bit
+ * patterns, 2-byte aligned), or null for a tensor without a shadow (biases, the log-std). */
+typedef struct ouz_adam_shadows {
+  uint16_t* shadow[OUZ_ADAM_MAX_TENSORS];
+} ouz_adam_shadows;
+int ouz_adam_clip_step_shadow(const ouz_adam_table* t, const ouz_adam_shadows* shadows, double lr, double beta1,
+                              double beta2, double eps, int64_t step, double max_norm, float* workspace, void* stream);
 
 /* PPO losses of one minibatch, forward + gradient for a unit upstream gradient in one call (the losses end the
  * graph).  Reductions are deterministic (fixed grid of OUZ_LOSS_BLOCKS per-block f64 partials summed in order).
@@ -511,6 +526,13 @@ int ouz_ppo_value_loss(const float* values, const float* returns, int32_t n, dou
 #define OUZ_COLSUM_BLOCKS 1024
 int ouz_tanh_bwd_bias(const float* dy, const float* y, int32_t rows, int32_t cols, float* workspace, float* dz,
                       float* dbias, void* stream);
+/* The same backward between bf16 activations (the learner's bf16 GEMM mode): dy, y and dz are bf16 (uint16_t bit
+ * patterns), dbias and the workspace f32.  dz = dy (1 - y^2) is formed in f32 and rounded to nearest even once;
+ * dbias sums the unrounded f32 dz, on the same fixed-order partials.  Each thread handles eight consecutive columns
+ * (16 bytes) where cols >= 8, four at cols = 4; dy / y / dz 16-byte aligned (8-byte at cols = 4), the workspace
+ * 16-byte aligned. */
+int ouz_tanh_bwd_bias_bf16(const uint16_t* dy, const uint16_t* y, int32_t rows, int32_t cols, float* workspace,
+                           uint16_t* dz, float* dbias, void* stream);
 
 /* The rollout policy's mean head and sample in one launch (RPO-LSTM/model.py:52-70, PPO/model.py:31-40 with
  * action None): mean = hidden W^T + b, action = mean + exp(logstd) eps, logprob = -1/2 sum eps^2 - sum logstd -

@@ -25,7 +25,7 @@ class OuzelumError(RuntimeError):
 
 
 # --- constants mirrored from include/ouzelum.h (checked against the library in tests) ---
-ABI_VERSION = 7
+ABI_VERSION = 8
 LAYOUT_VERSION = 4  # the ABI version whose state-slot rules (include/ouzelum.h "State slots") the layout follows
 TASK_OUZELUM, TASK_LEE_LANDED, TASK_EKF_LEE_LANDED, TASK_TRACKING, TASK_FAULT, TASK_MIXED, TASK_LANDING = range(7)
 NUM_TASKS = 7
@@ -102,6 +102,10 @@ class OuzAdamTable(ctypes.Structure):
                 ("exp_avg_sq", ctypes.c_void_p * ADAM_MAX_TENSORS)]
 
 
+class OuzAdamShadows(ctypes.Structure):   # ouz_adam_shadows: a bf16 shadow per table row, or null
+    _fields_ = [("shadow", ctypes.c_void_p * ADAM_MAX_TENSORS)]
+
+
 class OuzEpisodeRecord(ctypes.Structure):   # ouz_episode_record, 16 bytes
     _fields_ = [("tag", ctypes.c_int32), ("env_id", ctypes.c_int32), ("ret", ctypes.c_float), ("len", ctypes.c_int32)]
 
@@ -169,6 +173,11 @@ SIGNATURES = {
     "ouz_linear_tanh_small_k": (_I, [_P, _P, _P, _I, _I, _I, _P, _P]),
     "ouz_adam_clip_step": (_I, [ctypes.POINTER(OuzAdamTable), ctypes.c_double, ctypes.c_double, ctypes.c_double,
                                 ctypes.c_double, _I64, ctypes.c_double, _P, _P]),
+    "ouz_linear_tanh_small_k_bf16": (_I, [_P, _P, _P, _I, _I, _I, _P, _P]),
+    "ouz_tanh_bwd_bias_bf16": (_I, [_P, _P, _I, _I, _P, _P, _P, _P]),
+    "ouz_adam_clip_step_shadow": (_I, [ctypes.POINTER(OuzAdamTable), ctypes.POINTER(OuzAdamShadows), ctypes.c_double,
+                                       ctypes.c_double, ctypes.c_double, ctypes.c_double, _I64, ctypes.c_double, _P,
+                                       _P]),
 }
 LOSS_WS_DOUBLES = 10 * 256      # OUZ_LOSS_WS_DOUBLES
 COLSUM_BLOCKS = 1024            # OUZ_COLSUM_BLOCKS

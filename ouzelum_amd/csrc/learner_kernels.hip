@@ -492,6 +492,20 @@ __device__ __forceinline__ float ftanh(float x) {
 __device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
 __device__ __forceinline__ void st4(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
 
+// bf16 bit patterns for the learner's bf16 GEMM mode.  f32 -> bf16 rounds to nearest, ties to even, in integer
+// arithmetic (torch's c10::BFloat16 conversion: a NaN becomes 0x7FC0; values above the largest finite bf16's
+// midpoint carry into the exponent and give inf); bf16 -> f32 is exact.
+__device__ __forceinline__ uint32_t bf16_rne(float f) {
+  const uint32_t u = __float_as_uint(f);
+  if ((u & 0x7FFFFFFFu) > 0x7F800000u) return 0x7FC0u;
+  return (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;
+}
+__device__ __forceinline__ uint32_t bf16_pack(float lo, float hi) { return bf16_rne(lo) | (bf16_rne(hi) << 16); }
+__device__ __forceinline__ float bf16_lo(uint32_t p) { return __uint_as_float(p << 16); }
+__device__ __forceinline__ float bf16_hi(uint32_t p) { return __uint_as_float(p & 0xFFFF0000u); }
+// W bf16 values (W = 4: 8 bytes, W = 8: 16 bytes) as one access
+template <int W> struct alignas(2 * W) bf16xW { uint32_t p[W / 2]; };
+
 // Forward over T steps.  x_proj [T][B][4H] = x W_ih^T + b (pre-activation without the recurrent term), h0 / c0 [B][H],
 // keep [T][B] (1 - done: zeroes the carry entering step t), w [4H][H] (W_hh).  Writes, as the per-step path does,
 // act [T][B][4H] (activated gates), c_all / hid [T][B][H] and the masked carries hm / cm [T + 1][B][H] entering each
@@ -879,9 +893,13 @@ __global__ void __launch_bounds__(256) adam_sqnorm_kernel(ouz_adam_table t, int6
   if (threadIdx.x == 0) part[blockIdx.x] = s;
 }
 
-__global__ void __launch_bounds__(256) adam_step_kernel(ouz_adam_table t, int64_t ch, const float* __restrict__ part,
-                                                        int nparts, float lr_bc1, float w1, float beta2, float w2,
-                                                        float eps, float bc2_sqrt, float max_norm) {
+// SHADOW (ouz_adam_clip_step_shadow): the updated parameter is also stored as bf16 where its tensor has a shadow; the
+// f32 arithmetic and stores are the same statements either way
+template <bool SHADOW>
+__global__ void __launch_bounds__(256) adam_step_kernel(ouz_adam_table t, ouz_adam_shadows sh, int64_t ch,
+                                                        const float* __restrict__ part, int nparts, float lr_bc1,
+                                                        float w1, float beta2, float w2, float eps, float bc2_sqrt,
+                                                        float max_norm) {
   __shared__ float red[256];
   float coef = 1.0f;
   if (max_norm > 0.0f) {
@@ -896,6 +914,7 @@ __global__ void __launch_bounds__(256) adam_step_kernel(ouz_adam_table t, int64_
   float* __restrict__ p = t.param[i];
   float* __restrict__ m = t.exp_avg[i];
   float* __restrict__ v = t.exp_avg_sq[i];
+  uint16_t* __restrict__ s16 = SHADOW ? sh.shadow[i] : nullptr;
   for (int64_t e0 = lo + threadIdx.x; e0 < hi; e0 += 4 * 256) {
     float gv[4], mv[4], vv[4], pv[4];
 #pragma unroll
@@ -912,7 +931,9 @@ __global__ void __launch_bounds__(256) adam_step_kernel(ouz_adam_table t, int64_
       const float vn = vv[u] * beta2 + w2 * gc * gc;
       m[e] = mn;
       v[e] = vn;
-      p[e] = pv[u] + (-lr_bc1) * (mn / (sqrtf(vn) / bc2_sqrt + eps));
+      const float pn = pv[u] + (-lr_bc1) * (mn / (sqrtf(vn) / bc2_sqrt + eps));
+      p[e] = pn;
+      if (SHADOW && s16) s16[e] = (uint16_t)bf16_rne(pn);
     }
   }
 }
@@ -929,9 +950,13 @@ constexpr int kSmallKMax = 16;
 constexpr int kSmallKBlocks = 1024;
 constexpr int kSmallKChunk = 64;   // at most this many rows' inputs staged in LDS at a time (fewer below 32 K rows)
 
+// OutT float: W = 4.  OutT uint16_t (ouz_linear_tanh_small_k_bf16): the same staging and f32 arithmetic, each output
+// rounded to bf16 once at the store, W = 8 consecutive outputs of a row per thread (one 16-byte store) or, at
+// cols = 4, W = 4 (8 bytes).
+template <typename OutT, int W>
 __global__ void __launch_bounds__(256) linear_tanh_smallk_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                                  const float* __restrict__ b, int rows, int K, int cols,
-                                                                 int chunk, float* __restrict__ y) {
+                                                                 int chunk, OutT* __restrict__ y) {
   extern __shared__ float sw[];   // W^T [K][cols], b [cols], then the chunk's inputs [chunk][K]
   float* sx = sw + (K + 1) * cols;
   for (int e = threadIdx.x; e < K * cols; e += 256) {
@@ -939,8 +964,8 @@ __global__ void __launch_bounds__(256) linear_tanh_smallk_kernel(const float* __
     sw[e] = w[(size_t)c * K + k];
   }
   for (int c = threadIdx.x; c < cols; c += 256) sw[K * cols + c] = b[c];
-  const int tpr = cols >> 2, rpb = 256 / tpr;   // threads per row, rows per pass (cols a power of two)
-  const int c4 = (int)threadIdx.x % tpr, rs = (int)threadIdx.x / tpr;
+  const int tpr = cols / W, rpb = 256 / tpr;   // threads per row, rows per pass (cols a power of two)
+  const int cw = (int)threadIdx.x % tpr, rs = (int)threadIdx.x / tpr;
   // the block's rows: contiguous chunks, dealt round robin over the blocks; each chunk's inputs are one coalesced
   // load into LDS, so no thread waits on its rows' input loads one after another
   for (int r0 = blockIdx.x * chunk; r0 < rows; r0 += gridDim.x * chunk) {
@@ -948,16 +973,89 @@ __global__ void __launch_bounds__(256) linear_tanh_smallk_kernel(const float* __
     __syncthreads();   // W^T / b written (first chunk), every thread done with the previous chunk's inputs
     for (int e = threadIdx.x; e < nr * K; e += 256) sx[e] = x[(size_t)r0 * K + e];
     __syncthreads();
-    const f32x4 bias = ld4(&sw[K * cols + 4 * c4]);
-    for (int r = rs; r < nr; r += rpb) {
-      f32x4 acc = bias;
-#pragma unroll 4
-      for (int k = 0; k < K; ++k) acc += sx[r * K + k] * ld4(&sw[k * cols + 4 * c4]);
-      f32x4 o;
+    f32x4 bias[W / 4];
 #pragma unroll
-      for (int i = 0; i < 4; ++i) o[i] = ftanh(acc[i]);
-      st4(y + (size_t)(r0 + r) * cols + 4 * c4, o);
+    for (int j = 0; j < W / 4; ++j) bias[j] = ld4(&sw[K * cols + W * cw + 4 * j]);
+    for (int r = rs; r < nr; r += rpb) {
+      f32x4 acc[W / 4];
+#pragma unroll
+      for (int j = 0; j < W / 4; ++j) acc[j] = bias[j];
+#pragma unroll 4
+      for (int k = 0; k < K; ++k) {
+        const float xv = sx[r * K + k];
+#pragma unroll
+        for (int j = 0; j < W / 4; ++j) acc[j] += xv * ld4(&sw[k * cols + W * cw + 4 * j]);
+      }
+#pragma unroll
+      for (int j = 0; j < W / 4; ++j)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) acc[j][i] = ftanh(acc[j][i]);
+      OutT* out = y + (size_t)(r0 + r) * cols + W * cw;
+      if constexpr (sizeof(OutT) == 4) {
+        st4(out, acc[0]);
+      } else {
+        bf16xW<W> o;
+#pragma unroll
+        for (int j = 0; j < W / 4; ++j) {
+          o.p[2 * j] = bf16_pack(acc[j][0], acc[j][1]);
+          o.p[2 * j + 1] = bf16_pack(acc[j][2], acc[j][3]);
+        }
+        *reinterpret_cast<bf16xW<W>*>(out) = o;
+      }
     }
+  }
+}
+
+// ---------------------------------------------------------------------------
+// tanh_bwd_colsum_kernel between bf16 activations (the learner's bf16 GEMM mode): dy, y and dz are bf16, W = 8
+// consecutive columns per thread (one 16-byte load each of dy and y, one 16-byte store) or, at cols = 4, W = 4.
+// dz = dy (1 - y^2) is formed in f32 from the exact f32 values of the operands and rounded once at the store; the
+// column partials add the unrounded f32 dz, on tanh_bwd_colsum_kernel's row split and summation order (per-block
+// partials, then colsum_finish_kernel), so dbias is deterministic and carries no bf16 rounding of dz.
+// ---------------------------------------------------------------------------
+template <int W>
+__global__ void __launch_bounds__(256) tanh_bwd_colsum_bf16_kernel(const uint16_t* __restrict__ dy,
+                                                                   const uint16_t* __restrict__ y,
+                                                                   uint16_t* __restrict__ dz, float* __restrict__ part,
+                                                                   int rows, int cols) {
+#pragma clang fp contract(off)
+  __shared__ float sh[256][W];
+  const int cg = cols / W;                  // column groups; 256 % cg == 0 (host-checked)
+  const int rp = 256 / cg;                  // rows per pass
+  const int cw = threadIdx.x % cg, r0 = threadIdx.x / cg;
+  const int per = (rows + kColBlocks - 1) / kColBlocks;
+  const int rb = blockIdx.x * per, re = min(rows, rb + per);
+  float acc[W];
+#pragma unroll
+  for (int i = 0; i < W; ++i) acc[i] = 0.0f;
+#pragma unroll 4
+  for (int r = rb + r0; r < re; r += rp) {
+    const size_t k = (size_t)r * cg + cw;
+    const bf16xW<W> g = reinterpret_cast<const bf16xW<W>*>(dy)[k];
+    const bf16xW<W> t = reinterpret_cast<const bf16xW<W>*>(y)[k];
+    bf16xW<W> o;
+#pragma unroll
+    for (int j = 0; j < W / 2; ++j) {
+      const float t0 = bf16_lo(t.p[j]), t1 = bf16_hi(t.p[j]);
+      const float z0 = bf16_lo(g.p[j]) * (1.0f - t0 * t0);
+      const float z1 = bf16_hi(g.p[j]) * (1.0f - t1 * t1);
+      o.p[j] = bf16_pack(z0, z1);
+      acc[2 * j] += z0;
+      acc[2 * j + 1] += z1;
+    }
+    reinterpret_cast<bf16xW<W>*>(dz)[k] = o;
+  }
+#pragma unroll
+  for (int i = 0; i < W; ++i) sh[threadIdx.x][i] = acc[i];
+  __syncthreads();
+  if (r0 == 0) {
+    for (int q = 1; q < rp; ++q)
+#pragma unroll
+      for (int i = 0; i < W; ++i) acc[i] += sh[q * cg + cw][i];
+#pragma unroll
+    for (int j = 0; j < W / 4; ++j)
+      st4(part + (size_t)blockIdx.x * cols + W * cw + 4 * j,
+          f32x4{acc[4 * j], acc[4 * j + 1], acc[4 * j + 2], acc[4 * j + 3]});
   }
 }
 
@@ -1169,8 +1267,9 @@ int ouz_policy_sample(const float* hidden, const float* w, const float* b, const
 }
 
 
-int ouz_adam_clip_step(const ouz_adam_table* t, double lr, double beta1, double beta2, double eps, int64_t step,
-                       double max_norm, float* workspace, void* stream) {
+// ouz_adam_clip_step (shadows null) and ouz_adam_clip_step_shadow
+static int adam_clip_step(const ouz_adam_table* t, const ouz_adam_shadows* shadows, double lr, double beta1,
+                          double beta2, double eps, int64_t step, double max_norm, float* workspace, void* stream) {
   if (!t || !workspace) return set_error(OUZ_ERR_INVALID, "ouz_adam_clip_step: null table or workspace");
   if (t->n_tensors < 1 || t->n_tensors > OUZ_ADAM_MAX_TENSORS)
     return set_error(OUZ_ERR_INVALID, "ouz_adam_clip_step: 1 to OUZ_ADAM_MAX_TENSORS tensors");
@@ -1190,27 +1289,89 @@ int ouz_adam_clip_step(const ouz_adam_table* t, double lr, double beta1, double 
   const hipStream_t s = (hipStream_t)stream;
   if (max_norm > 0.0)
     hipLaunchKernelGGL(adam_sqnorm_kernel, dim3((unsigned)chunks), dim3(256), 0, s, *t, ch, workspace);
-  hipLaunchKernelGGL(adam_step_kernel, dim3((unsigned)chunks), dim3(256), 0, s, *t, ch, workspace, (int)chunks,
-                     (float)(lr / bc1), (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps,
-                     (float)std::sqrt(bc2), (float)max_norm);
+  if (shadows)
+    hipLaunchKernelGGL(adam_step_kernel<true>, dim3((unsigned)chunks), dim3(256), 0, s, *t, *shadows, ch, workspace,
+                       (int)chunks, (float)(lr / bc1), (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2),
+                       (float)eps, (float)std::sqrt(bc2), (float)max_norm);
+  else
+    hipLaunchKernelGGL(adam_step_kernel<false>, dim3((unsigned)chunks), dim3(256), 0, s, *t, ouz_adam_shadows{}, ch,
+                       workspace, (int)chunks, (float)(lr / bc1), (float)(1.0 - beta1), (float)beta2,
+                       (float)(1.0 - beta2), (float)eps, (float)std::sqrt(bc2), (float)max_norm);
   return launch_status("adam_step_kernel");
 }
 
+int ouz_adam_clip_step(const ouz_adam_table* t, double lr, double beta1, double beta2, double eps, int64_t step,
+                       double max_norm, float* workspace, void* stream) {
+  return adam_clip_step(t, nullptr, lr, beta1, beta2, eps, step, max_norm, workspace, stream);
+}
 
-int ouz_linear_tanh_small_k(const float* x, const float* w, const float* b, int32_t rows, int32_t K, int32_t cols,
-                            float* y, void* stream) {
+int ouz_adam_clip_step_shadow(const ouz_adam_table* t, const ouz_adam_shadows* shadows, double lr, double beta1,
+                              double beta2, double eps, int64_t step, double max_norm, float* workspace,
+                              void* stream) {
+  if (!shadows) return set_error(OUZ_ERR_INVALID, "ouz_adam_clip_step_shadow: null shadow table");
+  if (t && t->n_tensors >= 1 && t->n_tensors <= OUZ_ADAM_MAX_TENSORS)
+    for (int i = 0; i < t->n_tensors; ++i)
+      if (reinterpret_cast<uintptr_t>(shadows->shadow[i]) & 1u)
+        return set_error(OUZ_ERR_INVALID, "ouz_adam_clip_step_shadow: shadows must be 2-byte aligned");
+  return adam_clip_step(t, shadows, lr, beta1, beta2, eps, step, max_norm, workspace, stream);
+}
+
+
+extern "C++" {
+// ouz_linear_tanh_small_k (OutT float) and ouz_linear_tanh_small_k_bf16 (OutT uint16_t)
+template <typename OutT>
+static int linear_tanh_small_k(const char* name, const float* x, const float* w, const float* b, int32_t rows, int32_t K,
+                               int32_t cols, OutT* y, void* stream) {
+  const std::string n(name);
   if (rows < 0 || K < 1 || K > kSmallKMax || cols < 4 || cols > 1024 || (cols & (cols - 1)))
-    return set_error(OUZ_ERR_INVALID, "ouz_linear_tanh_small_k: rows >= 0, 1 <= K <= 16, cols a power of two in [4, 1024]");
+    return set_error(OUZ_ERR_INVALID, n + ": rows >= 0, 1 <= K <= 16, cols a power of two in [4, 1024]");
   if (rows == 0) return OUZ_OK;   // (torch's empty tensors have null data pointers)
-  if (!x || !w || !b || !y) return set_error(OUZ_ERR_INVALID, "ouz_linear_tanh_small_k: null buffer");
-  if (!aligned16(y)) return set_error(OUZ_ERR_INVALID, "ouz_linear_tanh_small_k: y must be 16-byte aligned");
+  if (!x || !w || !b || !y) return set_error(OUZ_ERR_INVALID, n + ": null buffer");
+  if (!aligned16(y)) return set_error(OUZ_ERR_INVALID, n + ": y must be 16-byte aligned");
   // chunks of 8-64 rows: at least ~512 blocks where the rows allow (the rollout's 8 192 rows: 16-row chunks)
   const int chunk = std::max(8, std::min(kSmallKChunk, (rows + 511) / 512));
   const int blocks = std::min((rows + chunk - 1) / chunk, kSmallKBlocks);
-  hipLaunchKernelGGL(linear_tanh_smallk_kernel, dim3(blocks), dim3(256),
-                     ((size_t)(K + 1) * cols + (size_t)chunk * K) * sizeof(float), (hipStream_t)stream, x, w, b, rows, K,
-                     cols, chunk, y);
+  const size_t lds = ((size_t)(K + 1) * cols + (size_t)chunk * K) * sizeof(float);
+  const hipStream_t s = (hipStream_t)stream;
+  if constexpr (sizeof(OutT) == 4)
+    hipLaunchKernelGGL((linear_tanh_smallk_kernel<float, 4>), dim3(blocks), dim3(256), lds, s, x, w, b, rows, K, cols,
+                       chunk, y);
+  else if (cols >= 8)
+    hipLaunchKernelGGL((linear_tanh_smallk_kernel<uint16_t, 8>), dim3(blocks), dim3(256), lds, s, x, w, b, rows, K, cols,
+                       chunk, y);
+  else
+    hipLaunchKernelGGL((linear_tanh_smallk_kernel<uint16_t, 4>), dim3(blocks), dim3(256), lds, s, x, w, b, rows, K, cols,
+                       chunk, y);
   return launch_status("linear_tanh_smallk_kernel");
+}
+}  // extern "C++"
+
+int ouz_linear_tanh_small_k(const float* x, const float* w, const float* b, int32_t rows, int32_t K, int32_t cols,
+                            float* y, void* stream) {
+  return linear_tanh_small_k("ouz_linear_tanh_small_k", x, w, b, rows, K, cols, y, stream);
+}
+
+int ouz_linear_tanh_small_k_bf16(const float* x, const float* w, const float* b, int32_t rows, int32_t K,
+                                 int32_t cols, uint16_t* y, void* stream) {
+  return linear_tanh_small_k("ouz_linear_tanh_small_k_bf16", x, w, b, rows, K, cols, y, stream);
+}
+
+int ouz_tanh_bwd_bias_bf16(const uint16_t* dy, const uint16_t* y, int32_t rows, int32_t cols, float* workspace,
+                           uint16_t* dz, float* dbias, void* stream) {
+  if (rows <= 0 || cols < 4 || cols > 1024 || (cols & (cols - 1)))
+    return set_error(OUZ_ERR_INVALID, "ouz_tanh_bwd_bias_bf16: rows > 0 and cols a power of two in [4, 1024]");
+  if (!dy || !y || !workspace || !dz || !dbias)
+    return set_error(OUZ_ERR_INVALID, "ouz_tanh_bwd_bias_bf16: null buffer");
+  const uintptr_t act = reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(dz);
+  if ((act & (cols >= 8 ? 15u : 7u)) || !aligned16(workspace))
+    return set_error(OUZ_ERR_INVALID, "ouz_tanh_bwd_bias_bf16: buffers must be 16-byte aligned (dy / y / dz 8-byte at 4 columns)");
+  const hipStream_t s = (hipStream_t)stream;
+  if (cols >= 8)
+    hipLaunchKernelGGL(tanh_bwd_colsum_bf16_kernel<8>, dim3(kColBlocks), dim3(256), 0, s, dy, y, dz, workspace, rows, cols);
+  else
+    hipLaunchKernelGGL(tanh_bwd_colsum_bf16_kernel<4>, dim3(kColBlocks), dim3(256), 0, s, dy, y, dz, workspace, rows, cols);
+  hipLaunchKernelGGL(colsum_finish_kernel, dim3(grid(cols, 16)), dim3(256), 0, s, workspace, cols, dbias);
+  return launch_status("tanh_bwd_colsum_bf16_kernel");
 }
 
 }  // extern "C"

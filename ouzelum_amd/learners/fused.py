@@ -16,6 +16,9 @@
 * ``PolicyLoss`` / ``ValueLoss``: the PPO losses of a minibatch (``RPO-LSTM/agent.py:86-110``)
   as one HIP forward each that also writes the loss's input gradients (``ouz_ppo_policy_loss``,
   ``ouz_ppo_value_loss``), replacing ~60 element-wise and reduction launches per minibatch.
+* ``LinearTanhBf16`` / ``SplitKLinearBf16`` / ``Bf16Shadows``: the same trunk blocks of the learner's opt-in bf16 GEMM
+  mode (bf16 operands and activations, f32 accumulation, f32 master weights with bf16 shadows that ``ClipAdam``'s step
+  launch rewrites: ``ouz_linear_tanh_small_k_bf16``, ``ouz_tanh_bwd_bias_bf16``, ``ouz_adam_clip_step_shadow``).
 """
 import os
 
@@ -123,6 +126,166 @@ class LinearTanh(torch.autograd.Function):
         return dx, dw, db
 
 
+# ---------------------------------------------------------------------------------------------------------------
+# The bf16 GEMM mode of the update (PPOLearner(gemm_dtype="bf16"); DESIGN.md §9.1 "Precision contract").  The master
+# weights stay f32; each 2-D weight has a bf16 shadow that the optimizer step rewrites (ClipAdam).  The big products
+# take bf16 operands with f32 accumulation, activations between trunk layers are bf16, weight-gradient slabs come
+# out of the library in f32 (``out_dtype``) and are summed in f32.
+# ---------------------------------------------------------------------------------------------------------------
+BF16 = torch.bfloat16
+
+
+class Bf16Shadows:
+    """The bf16 shadows of a network's GEMM weights (its 2-D parameters): ``of(p)`` is the round-to-nearest-even bf16
+    of the f32 parameter ``p``, or None for a tensor without one (biases, the log-std).  ``refresh()`` rewrites them
+    all from the parameters in one multi-tensor cast (after ``load`` / a broadcast / a torch optimizer step);
+    ``ClipAdam`` keeps them current inside its own step launch."""
+
+    def __init__(self, module):
+        self.params = [p for name, p in module.named_parameters()
+                       if p.dim() == 2 and "weight" in name.rsplit(".", 1)[-1]]
+        if any(p.dtype != torch.float32 or p.device.type != "cuda" for p in self.params):
+            raise ValueError("Bf16Shadows: f32 parameters on a HIP device (the bf16 GEMM mode has no CPU form)")
+        self.shadows = [torch.empty_like(p, dtype=BF16) for p in self.params]
+        self._by_id = {id(p): s for p, s in zip(self.params, self.shadows)}
+        self.refresh()
+
+    def of(self, p):
+        return self._by_id.get(id(p))
+
+    @torch.no_grad()
+    def refresh(self):
+        torch._foreach_copy_(self.shadows, [p.detach() for p in self.params])
+
+
+def splitk_wgrad_bf16(dy, x):
+    """``splitk_wgrad`` of bf16 operands: every slab product leaves the library in f32 (f32 accumulation,
+    ``out_dtype``) and the slabs are summed in f32."""
+    k, n = dy.shape
+    m = x.shape[1]
+    s = _splits(k, max(1, (n // 64) * (m // 64)))
+    if s == 1:
+        return torch.mm(dy.t(), x, out_dtype=torch.float32)
+    return torch.bmm(dy.view(s, k // s, n).transpose(1, 2), x.view(s, k // s, m), out_dtype=torch.float32).sum(0)
+
+
+def _as_bf16(t):
+    return t if t.dtype == BF16 else t.to(BF16)
+
+
+class SplitKLinearBf16(torch.autograd.Function):
+    """y = x Wᵀ + b in f32 from bf16 operands (f32 accumulation, the result never rounded to bf16): the LSTM's input
+    projection and the mean / value heads of the bf16 mode.  ``shadow`` is W's bf16 shadow; the gradients go to the
+    f32 ``weight`` / ``bias``.  Backward: the f32 dy is cast to bf16 once for dx = dy W (bf16, the trunk's next dy) and
+    the split-K dW = dyᵀ x (f32); db sums the f32 dy."""
+
+    @staticmethod
+    def forward(ctx, x, weight, shadow, bias):
+        x = _as_bf16(x)
+        ctx.save_for_backward(x, shadow)
+        return torch.addmm(bias, x, shadow.t(), out_dtype=torch.float32)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, shadow = ctx.saved_tensors
+        dy = dy.contiguous()
+        db = dy.sum(0) if ctx.needs_input_grad[3] else None
+        dy16 = _as_bf16(dy)
+        dx = dy16.mm(shadow) if ctx.needs_input_grad[0] else None
+        dw = splitk_wgrad_bf16(dy16, x) if ctx.needs_input_grad[1] else None
+        return dx, dw, None, db
+
+
+def linear_tanh_small_k_bf16(x, weight, bias):
+    """``linear_tanh_small_k`` with a bf16 result (``ouz_linear_tanh_small_k_bf16``: f32 inputs, weights and arithmetic,
+    one rounding at the store; no autograd)."""
+    x = x.contiguous()
+    w, b = weight.detach().contiguous(), bias.detach().contiguous()
+    y = torch.empty((x.shape[0], w.shape[0]), dtype=BF16, device=x.device)
+    L.check(L.lib.ouz_linear_tanh_small_k_bf16(x.data_ptr(), w.data_ptr(), b.data_ptr(), x.shape[0], w.shape[1],
+                                               w.shape[0], y.data_ptr(), L.stream_ptr(x.device)),
+            "ouz_linear_tanh_small_k_bf16")
+    return y
+
+
+def tanh_bwd_bias_bf16(dy, y):
+    """(dz bf16, dbias f32) of y = tanh(z) between bf16 activations (``ouz_tanh_bwd_bias_bf16``)."""
+    rows, cols = y.shape
+    dz = torch.empty_like(y)
+    db = torch.empty(cols, device=y.device)
+    ws = torch.empty(L.COLSUM_BLOCKS * cols, device=y.device)
+    L.check(L.lib.ouz_tanh_bwd_bias_bf16(dy.data_ptr(), y.data_ptr(), rows, cols, ws.data_ptr(), dz.data_ptr(),
+                                         db.data_ptr(), L.stream_ptr(y.device)), "ouz_tanh_bwd_bias_bf16")
+    return dz, db
+
+
+class LinearTanhBf16(torch.autograd.Function):
+    """y = tanh(x Wᵀ + b) with a bf16 result.  A first layer (f32 x of K <= 16 inputs) is one HIP pass on the f32
+    weights (``linear_tanh_small_k_bf16``); a bf16 x takes the bf16 GEMM on W's shadow (f32 accumulation, the bias
+    added in the GEMM's epilogue before its one rounding) and torch's in-place tanh.  Backward: dz (bf16) and db (f32,
+    from the unrounded dz) in one HIP pass (``tanh_bwd_bias_bf16``), dx = dz W in bf16, the split-K dW in f32."""
+
+    @staticmethod
+    def forward(ctx, x, weight, shadow, bias):
+        if x.dtype == torch.float32:
+            if not smallk_ok(x, weight, bias):
+                raise ValueError("LinearTanhBf16: an f32 input must be a first layer of K <= 16 inputs")
+            y = linear_tanh_small_k_bf16(x, weight, bias)
+            x = x.to(BF16)     # the K-column operand of this layer's dW product
+        else:
+            y = torch.addmm(bias.detach().to(BF16), x, shadow.t())
+            torch.tanh_(y)
+        ctx.save_for_backward(x, shadow, y)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, shadow, y = ctx.saved_tensors
+        dz, db = tanh_bwd_bias_bf16(_as_bf16(dy.contiguous()), y)
+        dx = dz.mm(shadow) if ctx.needs_input_grad[0] else None
+        dw = splitk_wgrad_bf16(dz, x) if ctx.needs_input_grad[1] else None
+        return dx, dw, None, db
+
+
+def linear_bf16(x, layer, shadows):
+    """nn.Linear forward of the bf16 mode: f32 out of bf16 operands (``SplitKLinearBf16``).  A head of fewer than
+    four columns (the 1-column value head) takes the f32 ``SplitKLinear`` on the upcast activations instead: the
+    library's bf16 product with an f32 result spends 17.8 ms of HOST time per call at one output column
+    (docs/HISTORY.md round 12), and the head is no large product either way."""
+    if layer.out_features < 4:
+        return SplitKLinear.apply(x.float(), layer.weight, layer.bias)
+    return SplitKLinearBf16.apply(x, layer.weight, shadows.of(layer.weight), layer.bias)
+
+
+def bf16_ok(seq, x, min_rows, shadows):
+    """The bf16 mode applies to this trunk call: the learner asked for it (``shadows``), the call is the update's
+    (autograd on, >= min_rows rows on the GPU), and the trunk is Linear + Tanh pairs of fusable widths whose first
+    layer is the small-K one, with at most one Linear head after them."""
+    if shadows is None or not _fused_ok(x, min_rows) or x.dtype != torch.float32:
+        return False
+    mods = list(seq)
+    n_pairs = 0
+    while (2 * n_pairs + 1 < len(mods) and isinstance(mods[2 * n_pairs], torch.nn.Linear)
+           and isinstance(mods[2 * n_pairs + 1], torch.nn.Tanh)):
+        if not _tanh_fusable(mods[2 * n_pairs], x, min_rows):
+            return False
+        n_pairs += 1
+    rest = mods[2 * n_pairs:]
+    return (n_pairs >= 1 and smallk_ok(x, mods[0].weight, mods[0].bias)
+            and (not rest or (len(rest) == 1 and isinstance(rest[0], torch.nn.Linear) and rest[0].bias is not None)))
+
+
+def run_mlp_bf16(seq, x, shadows):
+    """``run_mlp`` in the bf16 mode (``bf16_ok``): bf16 out of a trunk that ends in a Tanh, f32 out of a Linear head."""
+    mods = list(seq)
+    i = 0
+    while i + 1 < len(mods) and isinstance(mods[i + 1], torch.nn.Tanh):
+        m = mods[i]
+        x = LinearTanhBf16.apply(x, m.weight, shadows.of(m.weight), m.bias)
+        i += 2
+    return linear_bf16(x, mods[i], shadows) if i < len(mods) else x
+
+
 def _fused_ok(x, min_rows):
     return x.is_cuda and x.dim() == 2 and x.shape[0] >= min_rows and torch.is_grad_enabled()
 
@@ -140,10 +303,13 @@ def _tanh_fusable(layer, x, min_rows):
             and cols & (cols - 1) == 0)
 
 
-def run_mlp(seq, x, min_rows=8192):
+def run_mlp(seq, x, min_rows=8192, shadows=None):
     """Forward through an nn.Sequential of Linear / activation modules using ``linear``; a Linear followed by a
     Tanh becomes one ``LinearTanh`` where its rows and width allow, and, without autograd (the rollout's policy and
-    value calls), a first layer of K <= 16 inputs + its Tanh one ``linear_tanh_small_k`` pass at any row count."""
+    value calls), a first layer of K <= 16 inputs + its Tanh one ``linear_tanh_small_k`` pass at any row count.
+    ``shadows`` (a ``Bf16Shadows``: the learner's bf16 GEMM mode) sends the update's calls through ``run_mlp_bf16``."""
+    if bf16_ok(seq, x, min_rows, shadows):
+        return run_mlp_bf16(seq, x, shadows)
     mods = list(seq)
     i = 0
     while i < len(mods):
@@ -423,9 +589,11 @@ class ClipAdam:
     parameters, no weight decay / amsgrad / maximize): it keeps the parameter group, the hyper-parameters and the
     state (``step`` on the host, ``exp_avg``, ``exp_avg_sq``), so its ``state_dict`` / ``load_state_dict`` are the
     reference's checkpoint files unchanged; only its ``step`` is replaced.  The clipped gradients are not written
-    back into ``.grad`` (nothing reads them after the step)."""
+    back into ``.grad`` (nothing reads them after the step).  ``shadows`` (a ``Bf16Shadows`` of the same network, the
+    bf16 GEMM mode): the step launch also stores each updated weight's bf16 shadow (``ouz_adam_clip_step_shadow``;
+    parameters and moments are bit for bit those of the plain step)."""
 
-    def __init__(self, optimizer):
+    def __init__(self, optimizer, shadows=None):
         (group,) = optimizer.param_groups
         if (group["weight_decay"] or group["amsgrad"] or group["maximize"] or len(group["params"]) > L.ADAM_MAX_TENSORS
                 or any(p.dtype != torch.float32 or p.device.type != "cuda" for p in group["params"])):
@@ -433,10 +601,12 @@ class ClipAdam:
         self.optimizer = optimizer
         self.device = group["params"][0].device
         self.ws = torch.empty(L.ADAM_WS_FLOATS, device=self.device)
+        self.shadows = shadows
 
     def step(self, max_norm):
         (group,) = self.optimizer.param_groups
         table = L.OuzAdamTable()
+        shadow_table = L.OuzAdamShadows() if self.shadows is not None else None
         keep = []
         n, step = 0, None
         for p in group["params"]:
@@ -460,11 +630,20 @@ class ClipAdam:
             table.numel[n] = p.numel()
             table.grad[n], table.param[n] = g.data_ptr(), p.data_ptr()
             table.exp_avg[n], table.exp_avg_sq[n] = st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr()
+            if shadow_table is not None:
+                sh = self.shadows.of(p)
+                shadow_table.shadow[n] = None if sh is None else sh.data_ptr()
             n += 1
         if n == 0:
             return
         table.n_tensors = n
         b1, b2 = group["betas"]
+        if shadow_table is not None:
+            L.check(L.lib.ouz_adam_clip_step_shadow(table, shadow_table, float(group["lr"]), float(b1), float(b2),
+                                                    float(group["eps"]), step, float(max_norm or 0.0),
+                                                    self.ws.data_ptr(), L.stream_ptr(self.device)),
+                    "ouz_adam_clip_step_shadow")
+            return
         L.check(L.lib.ouz_adam_clip_step(table, float(group["lr"]), float(b1), float(b2), float(group["eps"]), step,
                                          float(max_norm or 0.0), self.ws.data_ptr(), L.stream_ptr(self.device)),
                 "ouz_adam_clip_step")

@@ -23,8 +23,8 @@ import torch
 import torch.nn as nn
 from torch.distributions.normal import Normal
 
-from .fused import (LSTMSequence, SplitKLinear, linear, lstm_sequence_carry_inplace, policy_sample, policy_sample_ok,
-                    run_mlp)
+from .fused import (LSTMSequence, SplitKLinear, SplitKLinearBf16, bf16_ok, linear, lstm_sequence_carry_inplace,
+                    policy_sample, policy_sample_ok, run_mlp, run_mlp_bf16)
 
 L_NUM_ACT = 4   # the action width ouz_policy_sample computes (OUZ_NUM_ACT)
 
@@ -53,6 +53,7 @@ class MLPActor(nn.Module):
             layer_init(nn.Linear(256, n_act), std=0.01),
         )
         self.actor_logstd = nn.Parameter(torch.zeros(1, n_act))
+        self.gemm_shadows = None   # a fused.Bf16Shadows: the learner's bf16 GEMM mode (PPOLearner sets it)
 
     def forward(self, state, action=None, eps=None):
         head = self.actor_mean[-1]
@@ -63,12 +64,12 @@ class MLPActor(nn.Module):
                 return policy_sample(hidden, head, self.actor_logstd, e)
             return _policy_head(torch.nn.functional.linear(hidden, head.weight, head.bias), self.actor_logstd,
                                 action, self.rpo_alpha, eps)
-        mean = run_mlp(self.actor_mean, state)
+        mean = run_mlp(self.actor_mean, state, shadows=self.gemm_shadows)
         return _policy_head(mean, self.actor_logstd, action, self.rpo_alpha, eps)
 
     def update_mean(self, state):
         """The mean the policy update scores its actions under (RPO's noise added), for ``fused.PolicyLoss``."""
-        return _rpo_mean(run_mlp(self.actor_mean, state), self.rpo_alpha)
+        return _rpo_mean(run_mlp(self.actor_mean, state, shadows=self.gemm_shadows), self.rpo_alpha)
 
 
 class LSTMActor(nn.Module):
@@ -93,6 +94,7 @@ class LSTMActor(nn.Module):
         self.actor_logstd = nn.Parameter(torch.zeros(1, n_act))
         # (h, c) buffers of shape (1, B, H) that inference calls write their final carry into (GraphedPolicy)
         self.carry_inplace = None
+        self.gemm_shadows = None   # a fused.Bf16Shadows: the learner's bf16 GEMM mode (PPOLearner sets it)
 
     def initial_state(self, num_envs, device):
         shape = (self.lstm.num_layers, num_envs, self.lstm.hidden_size)
@@ -101,15 +103,22 @@ class LSTMActor(nn.Module):
     def get_states(self, state, lstm_state, done):
         """(T·B, obs) trunk features -> (T·B, H) LSTM outputs; the carry of env b is zeroed
         before step t when done[t, b] (model.py:34-50).  Returns (hidden, (h, c))."""
-        feats = run_mlp(self.network, state)
+        # the bf16 GEMM mode (the update's calls only): bf16 trunk features into a bf16 input projection whose f32
+        # result enters the sequence kernels; the recurrence and the mean head stay f32
+        bf16 = bf16_ok(self.network, state, 8192, self.gemm_shadows)
+        feats = run_mlp_bf16(self.network, state, self.gemm_shadows) if bf16 else run_mlp(self.network, state)
         h, c = lstm_state
         B = h.shape[1]
         H = self.lstm.hidden_size
         bias = self.lstm.bias_ih_l0 + self.lstm.bias_hh_l0
         if feats.is_cuda:
             # HIP path: split-K input projection + fused cell kernels (fused.py)
-            x_proj = (SplitKLinear.apply(feats, self.lstm.weight_ih_l0, bias) if torch.is_grad_enabled()
-                      else torch.addmm(bias, feats, self.lstm.weight_ih_l0.t()))
+            if bf16:
+                x_proj = SplitKLinearBf16.apply(feats, self.lstm.weight_ih_l0,
+                                                self.gemm_shadows.of(self.lstm.weight_ih_l0), bias)
+            else:
+                x_proj = (SplitKLinear.apply(feats, self.lstm.weight_ih_l0, bias) if torch.is_grad_enabled()
+                          else torch.addmm(bias, feats, self.lstm.weight_ih_l0.t()))
             keep = (1.0 - done).float().view(-1, B)
             if self.carry_inplace is not None and not torch.is_grad_enabled():
                 # GraphedPolicy's static carry: the final (h, c) overwrite these buffers (no copies per step)
@@ -205,6 +214,7 @@ class Critic(nn.Module):
             layer_init(nn.Linear(256, 256)), nn.Tanh(),
             layer_init(nn.Linear(256, 1), std=1.0),
         )
+        self.gemm_shadows = None   # a fused.Bf16Shadows: the learner's bf16 GEMM mode (PPOLearner sets it)
 
     def forward(self, state):
-        return run_mlp(self.critic, state)
+        return run_mlp(self.critic, state, shadows=self.gemm_shadows)

@@ -20,6 +20,9 @@ Differences, all MI355X-side:
   parallel: rank 0's initial weights are broadcast and every optimizer step
   all-reduces one flattened gradient bucket over RCCL.  The reference learners are
   single-GPU.
+* ``gemm_dtype="bf16"`` (opt-in; DESIGN.md §9.1 "Precision contract"): the update's large trunk products take bf16
+  operands with f32 accumulation, from bf16 shadows of the f32 master weights that the optimizer step keeps current.
+  Everything without autograd (the rollout policy, the value pass before GAE, ``--play``) keeps the f32 weights.
 """
 import os
 
@@ -28,7 +31,7 @@ import torch.distributed as dist
 import torch.nn as nn
 
 from .. import _lib as L
-from .fused import ClipAdam, PolicyLoss, ValueLoss
+from .fused import Bf16Shadows, ClipAdam, PolicyLoss, ValueLoss
 from .gemm_tuning import enable_tuned_gemms
 from .models import Critic, LSTMActor, MLPActor
 
@@ -89,9 +92,17 @@ def gae(rewards, values, dones, next_value, next_done, gamma=0.99, lam=0.95):
     return ret, adv
 
 
+GEMM_DTYPES = ("f32", "bf16")
+
+
 class PPOLearner:
     def __init__(self, observation_space, action_space, num_envs, device, recurrent=True, rollout_steps=16,
-                 lr=0.0026, num_minibatches=2, update_epochs=4, tuned_gemms=True, rpo_alpha=None):
+                 lr=0.0026, num_minibatches=2, update_epochs=4, tuned_gemms=True, rpo_alpha=None, gemm_dtype="f32"):
+        if gemm_dtype not in GEMM_DTYPES:
+            raise ValueError(f"gemm_dtype must be one of {GEMM_DTYPES}, not {gemm_dtype!r}")
+        if gemm_dtype == "bf16" and torch.device(device).type != "cuda":
+            raise ValueError("gemm_dtype='bf16' needs a HIP device: the bf16 GEMM mode has no CPU form")
+        self.gemm_dtype = gemm_dtype
         self.obs_dim = observation_space
         self.act_dim = action_space
         self.num_envs = num_envs
@@ -124,6 +135,11 @@ class PPOLearner:
         self.critic = Critic(observation_space).to(self.device)
         broadcast_params(self.actor)
         broadcast_params(self.critic)
+        # the bf16 GEMM mode: bf16 shadows of both networks' GEMM weights, made after the broadcast
+        self._shadows = None
+        if gemm_dtype == "bf16":
+            self._shadows = (Bf16Shadows(self.actor), Bf16Shadows(self.critic))
+            self.actor.gemm_shadows, self.critic.gemm_shadows = self._shadows
         # fused Adam on the GPU: one multi-tensor kernel per optimizer step instead of the foreach
         # form's handful per parameter group (the update is launch-bound)
         fused = self.device.type == "cuda" and os.environ.get("OUZ_ADAM_FUSED", "1") != "0"
@@ -133,8 +149,15 @@ class PPOLearner:
         opt_kw = {"foreach": False} if clip_adam else {"fused": fused}
         self.actor_optimizer = torch.optim.Adam(self.actor.parameters(), lr=lr, eps=1e-5, **opt_kw)
         self.critic_optimizer = torch.optim.Adam(self.critic.parameters(), lr=lr, eps=1e-5, **opt_kw)
-        self._clip_adam = ((ClipAdam(self.actor_optimizer), ClipAdam(self.critic_optimizer)) if clip_adam
-                           else None)
+        sh = self._shadows or (None, None)
+        self._clip_adam = ((ClipAdam(self.actor_optimizer, sh[0]), ClipAdam(self.critic_optimizer, sh[1]))
+                           if clip_adam else None)
+
+    def refresh_shadows(self):
+        """The bf16 shadows from the current f32 weights, after anything but the optimizer step wrote the weights
+        (``load``, a broadcast, a caller's own copy); nothing to do in the f32 mode."""
+        for sh in self._shadows or ():
+            sh.refresh()
 
     # ------------------------------------------------------------------ rollout
     @torch.no_grad()
@@ -269,6 +292,8 @@ class PPOLearner:
         else:
             nn.utils.clip_grad_norm_(net.parameters(), self.max_grad_norm)
             optimizer.step()
+            if self._shadows is not None:     # one multi-tensor cast after torch's step
+                self._shadows[which].refresh()
 
     # -------------------------------------------------------------- checkpoints
     def save(self, filename):
@@ -287,6 +312,7 @@ class PPOLearner:
         self.actor.load_state_dict(torch.load(filename + "_actor", map_location=m, weights_only=True))
         self.actor_optimizer.load_state_dict(torch.load(filename + "_actor_optimizer", map_location=m,
                                                         weights_only=True))
+        self.refresh_shadows()
 
 
 class GraphedPolicy:

@@ -6,8 +6,8 @@
 Runs ``python -m ouzelum_amd.learners.train --learner L --POMDP P --pomdp_prob p`` once per (L, P, p), in the
 script's order (learner by learner; flicker, random_noise, flickering_and_random_noise), one after another, each a
 fresh child process, and stops at the first run that exits non-zero.  ``--dry_run`` prints the command lines and
-starts nothing.  Arguments this module does not know (``--env``, ``--num_envs``, ``--logdir``, ``--episode_log`` ...)
-are handed to every run.
+starts nothing.  Arguments this module does not know (``--env``, ``--num_envs``, ``--logdir``, ``--episode_log``,
+``--gemm_dtype`` ...) are handed to every run.
 """
 import argparse
 import shlex

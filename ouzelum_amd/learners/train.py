@@ -67,6 +67,9 @@ def parse_args(argv=None):
     p.add_argument("--checkpoint", default=None, help="checkpoint prefix (agent.save's filename)")
     p.add_argument("--learner", default=None, choices=list(LEARNERS),
                    help="one of the reference's seven learners (variants.py); not with --algo / --rollout_obs")
+    p.add_argument("--gemm_dtype", default="f32", choices=["f32", "bf16"],
+                   help="operand type of the update's large trunk products (bf16: f32 master weights and f32 "
+                        "accumulation; the rollout and --play stay f32)")
     p.add_argument("--episode_log", default="rollout_mean", choices=["rollout_mean", "per_episode"],
                    help="charts/* points: one mean per rollout, or the reference's one per episode (with --learner)")
     args = p.parse_args(argv)
@@ -210,7 +213,7 @@ def train(args, on_rollout=None):
     envs = EpisodeRecorder(ExtractObsWrapper(base), device, env_id0=off, capacity=3 * N)
     pomdp_w = POMDPWrapper(args.POMDP, args.pomdp_prob, seed=args.seed + 1, row_offset=off)
     agent = PPOLearner(base.observation_space, base.action_space, N, device, recurrent=v.recurrent,
-                       rollout_steps=T, rpo_alpha=v.rpo_alpha)
+                       rollout_steps=T, rpo_alpha=v.rpo_alpha, gemm_dtype=args.gemm_dtype)
     name, best = names(v, args.POMDP, args.pomdp_prob)
     ro = Rollout(envs, pomdp_w, agent, v, T, watch=on_rollout is not None)
 

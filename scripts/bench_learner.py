@@ -4,6 +4,7 @@ Times the reference loop shape (T = 16 rollout steps of policy + env.step, then 
 PPO update of 4 epochs x 2 minibatches) and splits wall time into rollout and update.
     python scripts/bench_learner.py --env Landing --num_envs 4096 --iters 20
     python scripts/bench_learner.py --env QuadFault --num_envs 8192 --learner RPO-LSTM [--episode_log per_episode]
+    python scripts/bench_learner.py --env QuadFault --num_envs 8192 --gemm_dtype bf16
 
 The rollout is train.py's (``learners.train.Rollout``).  ``--algo`` times it on the bare env, with no episode
 bookkeeping; ``--learner NAME`` in NAME's routing (learners/variants.py) with the bookkeeping train.py has, one
@@ -33,6 +34,7 @@ ap.add_argument("--iters", type=int, default=20)
 ap.add_argument("--warmup", type=int, default=3)
 ap.add_argument("--learner", default=None, choices=list(LEARNERS))
 ap.add_argument("--episode_log", default="rollout_mean", choices=["rollout_mean", "per_episode"])
+ap.add_argument("--gemm_dtype", default="f32", choices=["f32", "bf16"])
 a = ap.parse_args()
 v = VARIANTS[a.learner] if a.learner else legacy_variant(a.algo, "clean")
 per_episode = a.learner is not None and a.episode_log == "per_episode"
@@ -43,7 +45,8 @@ base = make(seed=0, task=a.env, num_envs=N, sim_device="cuda:0", rl_device="cuda
 env = ExtractObsWrapper(base)
 if a.learner:
     env = EpisodeRecorder(env, dev, capacity=3 * N)
-agent = PPOLearner(base.observation_space, base.action_space, N, dev, recurrent=v.recurrent, rpo_alpha=v.rpo_alpha)
+agent = PPOLearner(base.observation_space, base.action_space, N, dev, recurrent=v.recurrent, rpo_alpha=v.rpo_alpha,
+                   gemm_dtype=a.gemm_dtype)
 ro = Rollout(env, POMDPWrapper("flicker", 0.1, seed=1), agent, v, T)
 t_roll = t_upd = 0.0
 n_records = 0
@@ -66,7 +69,7 @@ for it in range(a.warmup + a.iters):
 steps = N * T * a.iters
 print(json.dumps({"algo": a.algo, **({"learner": a.learner, "episode_log": a.episode_log,
                                       "records": n_records} if a.learner else {}), "env": a.env, "num_envs": N,
-                  "iters": a.iters,
+                  "iters": a.iters, "gemm_dtype": a.gemm_dtype,
                   "train_env_steps_per_s": round(steps / (t_roll + t_upd), 1),
                   "rollout_env_steps_per_s": round(steps / t_roll, 1),
                   "rollout_ms_per_iter": round(t_roll / a.iters * 1e3, 3),

@@ -29,7 +29,7 @@ def category(name):
     if "lstm_seq" in name:
         return "lstm recurrence, one launch per direction (HIP, f32 MFMA)"
     if any(k in name for k in ("policy_loss_kernel", "value_loss_kernel", "loss_finish_kernel", "adv_moments_kernel",
-                                "tanh_bwd_colsum_kernel", "colsum_finish_kernel")):
+                                "tanh_bwd_colsum", "colsum_finish_kernel")):
         return "PPO losses + trunk tanh'/bias (HIP)"
     if "linear_tanh_smallk" in name:
         return "trunks' first layer + tanh (HIP, one pass)"

@@ -3,6 +3,7 @@
 # 30M, RPO-LSTM/main.py:22): the learners' default env (Landing), config D's consumer (QuadFault, 8192 envs)
 # and Ouzelum hover.  Writes the per-iteration CSVs (PPO/main.py:102-116 scalars) under gpurun_out/$TAG/,
 # then the learner throughput on config D.  Each run has its own time limit; stops at the first failure.
+# TRAIN_ARGS: further train.py arguments for every run (e.g. TRAIN_ARGS="--gemm_dtype bf16").
 set -u
 TAG=${TAG:-learn}
 OUT=gpurun_out/$TAG
@@ -11,7 +12,7 @@ mkdir -p $OUT
 for spec in ${RUNS:-Landing:4096 QuadFault:8192 Ouzelum:4096}; do
   env=${spec%%:*}; n=${spec##*:}
   timeout -k 10 ${RUN_TIMEOUT:-240} python -u -m ouzelum_amd.learners.train --env $env --num_envs $n \
-    --total_steps $STEPS --seed 0 --logdir $OUT/${env}_$n --no_checkpoints --quiet > $OUT/${env}_$n.log 2>&1
+    --total_steps $STEPS --seed 0 --logdir $OUT/${env}_$n --no_checkpoints --quiet ${TRAIN_ARGS:-} > $OUT/${env}_$n.log 2>&1
   rc=$?; echo "$env $n rc=$rc"; tail -n 3 $OUT/${env}_$n.log
   [ $rc -eq 0 ] || exit $rc
   f=$(ls $OUT/${env}_$n/*.csv); python - "$f" <<'EOF'
