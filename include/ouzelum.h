@@ -62,7 +62,7 @@
 extern "C" {
 #endif
 
-#define OUZ_ABI_VERSION 8  /* 2: trigger-class state layout of the estimator tasks (ouz_state_slots);
+#define OUZ_ABI_VERSION 9  /* 2: trigger-class state layout of the estimator tasks (ouz_state_slots);
                                3: 1344-id curriculum chunks of OUZ_TASK_MIXED with the class layout, ouz_env_slots;
                                4: physical domain randomisation (ouz_dr_physical, OUZ_I_RAND_STEP), DR noise
                                   frequency (ouz_dr_noise.frequency);
@@ -74,7 +74,9 @@ extern "C" {
                                7: per-env episode statistics with the per-episode record append (ouz_episode_step,
                                   ouz_episode_record);
                                8: the learner's bf16 GEMM mode (ouz_linear_tanh_small_k_bf16, ouz_tanh_bwd_bias_bf16,
-                                  ouz_adam_clip_step_shadow) */
+                                  ouz_adam_clip_step_shadow);
+                               9: the PPO update's options on the loss kernels (ouz_ppo_policy_loss_ent: entropy
+                                  bonus; ouz_ppo_value_loss_clipped: clipped value loss) */
 
 /* error codes */
 #define OUZ_OK 0
@@ -519,6 +521,26 @@ int ouz_ppo_policy_loss(const float* mean_z, const float* logstd, const float* a
  * returns) / n. */
 int ouz_ppo_value_loss(const float* values, const float* returns, int32_t n, double* workspace, float* dvalues,
                        float* loss, void* stream);
+/* The two losses with the update's options (agent.py:105-119), same conventions, workspace and launch counts (3 and
+ * 2) as the entries above; clip must be >= 0.
+ *
+ * Policy loss with the entropy bonus: loss = pg_loss - ent_coef * entropy, where pg_loss is the clipped loss above
+ * and entropy = mean over rows of Normal(mean_z, exp(logstd)).entropy().sum(1) = sum_j (0.5 + 0.5 log 2 pi +
+ * log(exp(logstd_j))) for the state-independent log-std, formed once in f64.  dlogstd_j = the clipped loss's
+ * gradient - ent_coef; dmean is unchanged.  pg_loss and entropy are single floats, always written.  With
+ * ent_coef == 0 the entropy term is skipped: loss, approx_kl, clipfrac, dmean and dlogstd are then bit for bit
+ * those of ouz_ppo_policy_loss. */
+int ouz_ppo_policy_loss_ent(const float* mean_z, const float* logstd, const float* actions, const float* old_logp,
+                            const float* advantages, int32_t n, float clip, int32_t norm_adv, float ent_coef,
+                            double* workspace, float* dmean, float* loss, float* approx_kl, float* clipfrac,
+                            float* dlogstd, float* pg_loss, float* entropy, void* stream);
+/* Clipped value loss (agent.py:105-114, clip_vloss True): per row u = (v - r)^2, vc = old + clamp(v - old, -clip,
+ * clip), c = (vc - r)^2; loss = 0.5 * mean(max(u, c)); dvalues = d loss / d values with torch's rules (maximum: the
+ * larger side takes the gradient, half each on u == c; clamp passes where -clip <= v - old <= clip, edges included);
+ * clipfrac = the share of rows with c > u (a diagnostic).  values, old_values, returns, dvalues [n]. */
+int ouz_ppo_value_loss_clipped(const float* values, const float* old_values, const float* returns, int32_t n,
+                               float clip, double* workspace, float* dvalues, float* loss, float* clipfrac,
+                               void* stream);
 
 /* Backward of y = tanh(x W^T + b) (the MLP trunks, RPO-LSTM/model.py:17-24,72-84): dz = dy (1 - y^2) and
  * dbias = column sums of dz in one pass.  dy, y, dz [rows][cols] row-major, cols a power of two in [4, 1024];

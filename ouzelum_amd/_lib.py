@@ -25,7 +25,7 @@ class OuzelumError(RuntimeError):
 
 
 # --- constants mirrored from include/ouzelum.h (checked against the library in tests) ---
-ABI_VERSION = 8
+ABI_VERSION = 9
 LAYOUT_VERSION = 4  # the ABI version whose state-slot rules (include/ouzelum.h "State slots") the layout follows
 TASK_OUZELUM, TASK_LEE_LANDED, TASK_EKF_LEE_LANDED, TASK_TRACKING, TASK_FAULT, TASK_MIXED, TASK_LANDING = range(7)
 NUM_TASKS = 7
@@ -168,6 +168,8 @@ SIGNATURES = {
     "ouz_lstm_seq_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P]),
     "ouz_ppo_policy_loss": (_I, [_P, _P, _P, _P, _P, _I, _F, _I, _P, _P, _P, _P, _P, _P, _P]),
     "ouz_ppo_value_loss": (_I, [_P, _P, _I, _P, _P, _P, _P]),
+    "ouz_ppo_policy_loss_ent": (_I, [_P, _P, _P, _P, _P, _I, _F, _I, _F, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "ouz_ppo_value_loss_clipped": (_I, [_P, _P, _P, _I, _F, _P, _P, _P, _P, _P]),
     "ouz_tanh_bwd_bias": (_I, [_P, _P, _I, _I, _P, _P, _P, _P]),
     "ouz_policy_sample": (_I, [_P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P]),
     "ouz_linear_tanh_small_k": (_I, [_P, _P, _P, _I, _I, _I, _P, _P]),

@@ -334,6 +334,95 @@ __global__ void __launch_bounds__(kLossThreads) loss_finish_kernel(const double*
   }
 }
 
+// The clipped value loss (agent.py:105-114, clip_vloss True): per row u = (v - r)^2, vc = old + clamp(v - old, -clip,
+// clip), c = (vc - r)^2, m = max(u, c); loss = 0.5 mean(m).  dv for a unit upstream gradient with torch's rules:
+// maximum gives each side the gradient where it is the larger and half each on u == c, clamp passes where
+// -clip <= v - old <= clip (edges included).  Per block: the sum of m and the count of rows with c > u.
+__global__ void __launch_bounds__(kLossThreads) value_loss_clipped_kernel(const float* __restrict__ v,
+                                                                          const float* __restrict__ old,
+                                                                          const float* __restrict__ r, int n,
+                                                                          float clip, float* __restrict__ dv,
+                                                                          double* __restrict__ part) {
+#pragma clang fp contract(off)
+  __shared__ double sh[kLossThreads / 64];
+  const float g = 0.5f * (1.0f / (float)n);   // d loss / d m
+  const float lo = -clip;
+  double s = 0.0, s_cf = 0.0;
+  for (int i = blockIdx.x * kLossThreads + threadIdx.x; i < n; i += kLossBlocks * kLossThreads) {
+    const float vi = v[i], oi = old[i], ri = r[i];
+    const float du = vi - ri;
+    const float u = du * du;
+    const float d = vi - oi;
+    const float vc = oi + fminf(fmaxf(d, lo), clip);
+    const float dc = vc - ri;
+    const float c = dc * dc;
+    s += (double)fmaxf(u, c);
+    s_cf += c > u ? 1.0 : 0.0;
+    const float gu = u > c ? g : (u == c ? g * 0.5f : 0.0f);
+    const float gc = c > u ? g : (u == c ? g * 0.5f : 0.0f);
+    const float through = (d >= lo && d <= clip) ? gc * (2.0f * dc) : 0.0f;   // c's side, through the clamp
+    dv[i] = gu * (2.0f * du) + through;
+  }
+  s = block_sum(s, sh);
+  s_cf = block_sum(s_cf, sh);
+  if (threadIdx.x == 0) { part[8 * blockIdx.x] = s; part[8 * blockIdx.x + 1] = s_cf; }
+}
+
+// The clipped value loss's finishing block: loss = 0.5 sum / n, clipfrac = count / n (block_sum's fixed tree each)
+__global__ void __launch_bounds__(kLossThreads) value_clipped_finish_kernel(const double* __restrict__ part, int n,
+                                                                            float* __restrict__ loss,
+                                                                            float* __restrict__ clipfrac) {
+  __shared__ double sh[kLossThreads / 64];
+  const double* p = part + 8 * threadIdx.x;
+  const double s = block_sum(p[0], sh);
+  const double cf = block_sum(p[1], sh);
+  if (threadIdx.x == 0) {
+    *loss = (float)(s * (0.5 / (double)n));
+    *clipfrac = (float)(cf / (double)n);
+  }
+}
+
+// policy_loss_kernel's finishing block with the entropy bonus (agent.py:118-119): the sums exactly as
+// loss_finish_kernel forms them (pg_loss, approx_kl, clipfrac and the four logstd sums), then
+//   entropy = sum_j (0.5 + 0.5 log 2 pi + log(exp(logstd_j)))   (Normal.entropy().sum(1); the log-std is
+//   state-independent, so every row, and with it the mean over rows, is this one value), in f64 from the same f32
+//   logf(expf(logstd_j)) the row kernel uses,
+//   loss = pg_loss - ent_coef entropy,  dlogstd_j = sum_j - ent_coef  (d entropy / d logstd_j = 1).
+// With ent_coef == 0 the term is skipped, not multiplied by zero: loss and dlogstd are loss_finish_kernel's bits.
+__global__ void __launch_bounds__(kLossThreads) policy_ent_finish_kernel(const double* __restrict__ part,
+                                                                         const float* __restrict__ logstd, int n,
+                                                                         float ent_coef, float* __restrict__ loss,
+                                                                         float* __restrict__ approx_kl,
+                                                                         float* __restrict__ clipfrac,
+                                                                         float* __restrict__ dlogstd,
+                                                                         float* __restrict__ pg_loss,
+                                                                         float* __restrict__ entropy) {
+#pragma clang fp contract(off)
+  __shared__ double sh[kLossThreads / 64];
+  const double* p = part + 8 * threadIdx.x;
+  const double scale = 1.0 / (double)n;
+  double ent = 0.0;
+#pragma unroll
+  for (int j = 0; j < OUZ_NUM_ACT; ++j) ent += (0.5 + 0.918938533204672742) + (double)logf(expf(logstd[j]));
+  for (int k = 0; k < 3 + OUZ_NUM_ACT; ++k) {
+    const double t = block_sum(p[k], sh);
+    if (threadIdx.x == 0) {
+      if (k == 0) {
+        const double pg = t * scale;
+        *pg_loss = (float)pg;
+        *entropy = (float)ent;
+        *loss = ent_coef == 0.0f ? (float)pg : (float)(pg - (double)ent_coef * ent);
+      } else if (k == 1) {
+        *approx_kl = (float)(t * scale);
+      } else if (k == 2) {
+        *clipfrac = (float)(t * scale);
+      } else {
+        dlogstd[k - 3] = ent_coef == 0.0f ? (float)t : (float)(t - (double)ent_coef);
+      }
+    }
+  }
+}
+
 // ---------------------------------------------------------------------------
 // Backward of y = tanh(x W^T + b) for the MLP trunks (RPO-LSTM/model.py:17-24,72-84): dz = dy (1 - y^2)
 // (torch's tanh_backward) and the bias gradient db = sum over rows of dz in the same pass, instead of a
@@ -1238,6 +1327,42 @@ int ouz_ppo_value_loss(const float* values, const float* returns, int32_t n, dou
   hipLaunchKernelGGL(loss_finish_kernel, dim3(1), dim3(kLossThreads), 0, s, workspace, 1, 0.5 / (double)n, loss, nullptr, nullptr,
                      nullptr);
   return launch_status("value_loss_kernel");
+}
+
+int ouz_ppo_policy_loss_ent(const float* mean_z, const float* logstd, const float* actions, const float* old_logp,
+                            const float* advantages, int32_t n, float clip, int32_t norm_adv, float ent_coef,
+                            double* workspace, float* dmean, float* loss, float* approx_kl, float* clipfrac,
+                            float* dlogstd, float* pg_loss, float* entropy, void* stream) {
+  if (n <= 0 || (norm_adv && n < 2)) return set_error(OUZ_ERR_INVALID, "ouz_ppo_policy_loss_ent: n must be > 0 (> 1 with norm_adv)");
+  if (!(clip >= 0.0f)) return set_error(OUZ_ERR_INVALID, "ouz_ppo_policy_loss_ent: clip must be >= 0");
+  if (!mean_z || !logstd || !actions || !old_logp || !advantages || !workspace || !dmean || !loss || !approx_kl ||
+      !clipfrac || !dlogstd || !pg_loss || !entropy)
+    return set_error(OUZ_ERR_INVALID, "ouz_ppo_policy_loss_ent: null buffer");
+  if (((reinterpret_cast<uintptr_t>(mean_z) | reinterpret_cast<uintptr_t>(actions) | reinterpret_cast<uintptr_t>(dmean)) & 15u))
+    return set_error(OUZ_ERR_INVALID, "ouz_ppo_policy_loss_ent: mean_z / actions / dmean must be 16-byte aligned");
+  const hipStream_t s = (hipStream_t)stream;
+  double* adv_part = workspace;
+  double* part = workspace + 2 * kLossBlocks;
+  if (norm_adv) hipLaunchKernelGGL(adv_moments_kernel, dim3(kLossBlocks), dim3(kLossThreads), 0, s, advantages, n, adv_part);
+  hipLaunchKernelGGL(policy_loss_kernel, dim3(kLossBlocks), dim3(kLossThreads), 0, s, mean_z, logstd, actions, old_logp,
+                     advantages, n, clip, norm_adv, adv_part, dmean, part);
+  hipLaunchKernelGGL(policy_ent_finish_kernel, dim3(1), dim3(kLossThreads), 0, s, part, logstd, n, ent_coef, loss,
+                     approx_kl, clipfrac, dlogstd, pg_loss, entropy);
+  return launch_status("policy_loss_kernel");
+}
+
+int ouz_ppo_value_loss_clipped(const float* values, const float* old_values, const float* returns, int32_t n,
+                               float clip, double* workspace, float* dvalues, float* loss, float* clipfrac,
+                               void* stream) {
+  if (n <= 0) return set_error(OUZ_ERR_INVALID, "ouz_ppo_value_loss_clipped: n must be > 0");
+  if (!(clip >= 0.0f)) return set_error(OUZ_ERR_INVALID, "ouz_ppo_value_loss_clipped: clip must be >= 0");
+  if (!values || !old_values || !returns || !workspace || !dvalues || !loss || !clipfrac)
+    return set_error(OUZ_ERR_INVALID, "ouz_ppo_value_loss_clipped: null buffer");
+  const hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(value_loss_clipped_kernel, dim3(kLossBlocks), dim3(kLossThreads), 0, s, values, old_values, returns,
+                     n, clip, dvalues, workspace);
+  hipLaunchKernelGGL(value_clipped_finish_kernel, dim3(1), dim3(kLossThreads), 0, s, workspace, n, loss, clipfrac);
+  return launch_status("value_loss_clipped_kernel");
 }
 
 int ouz_tanh_bwd_bias(const float* dy, const float* y, int32_t rows, int32_t cols, float* workspace, float* dz,

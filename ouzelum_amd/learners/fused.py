@@ -390,6 +390,73 @@ class ValueLoss(torch.autograd.Function):
         return dv * g, None
 
 
+class PolicyLossEnt(torch.autograd.Function):
+    """``PolicyLoss`` with the entropy bonus (agent.py:118-119), ``ouz_ppo_policy_loss_ent``: (mean_z, logstd,
+    actions, old_logp, advantages, clip, norm_adv, ent_coef) -> (actor_loss, pg_loss, entropy, approx_kl, clipfrac),
+    0-dim; actor_loss = pg_loss - ent_coef * entropy is the differentiable one.  Same three launches."""
+
+    @staticmethod
+    def forward(ctx, mean_z, logstd, actions, old_logp, adv, clip, norm_adv, ent_coef):
+        dev = mean_z.device
+        n = mean_z.shape[0]
+        mz, ls, act, old, a = (t.detach().contiguous() for t in (mean_z, logstd, actions, old_logp, adv))
+        for t, name in ((mz, "mean_z"), (ls, "logstd"), (act, "actions"), (old, "old_logp"), (a, "advantages")):
+            L.require_hip_tensor(t, name)
+            if t.dtype != torch.float32:
+                raise ValueError(f"PolicyLossEnt: {name} must be float32")
+        if mz.shape != (n, L.NUM_ACT) or act.shape != (n, L.NUM_ACT) or ls.numel() != L.NUM_ACT \
+                or old.numel() != n or a.numel() != n:
+            raise ValueError("PolicyLossEnt: mean_z / actions (n, 4), logstd 4 values, old_logp / advantages n values")
+        dmean = torch.empty_like(mz)
+        loss, kl, cf, pg, ent = (torch.empty((), device=dev) for _ in range(5))
+        dls = torch.empty(logstd.shape, device=dev)
+        ws = torch.empty(L.LOSS_WS_DOUBLES, dtype=torch.float64, device=dev)
+        L.check(L.lib.ouz_ppo_policy_loss_ent(mz.data_ptr(), ls.data_ptr(), act.data_ptr(), old.data_ptr(),
+                                              a.data_ptr(), n, float(clip), int(bool(norm_adv)), float(ent_coef),
+                                              ws.data_ptr(), dmean.data_ptr(), loss.data_ptr(), kl.data_ptr(),
+                                              cf.data_ptr(), dls.data_ptr(), pg.data_ptr(), ent.data_ptr(),
+                                              L.stream_ptr(dev)), "ouz_ppo_policy_loss_ent")
+        ctx.save_for_backward(dmean, dls)
+        ctx.mark_non_differentiable(pg, ent, kl, cf)
+        ctx.set_materialize_grads(False)
+        return loss, pg, ent, kl, cf
+
+    @staticmethod
+    def backward(ctx, g, *_):
+        dmean, dls = ctx.saved_tensors
+        return dmean * g, dls * g, None, None, None, None, None, None
+
+
+class ValueLossClipped(torch.autograd.Function):
+    """(values (n,), old_values (n,), returns (n,), clip) -> (v_loss, clipfrac), 0-dim: the clipped value loss
+    (agent.py:105-114), ``ouz_ppo_value_loss_clipped``; clipfrac (the share of rows where the clipped term is the
+    larger) is a diagnostic.  Same two launches as ``ValueLoss``."""
+
+    @staticmethod
+    def forward(ctx, values, old_values, returns, clip):
+        dev = values.device
+        v, o, r = (t.detach().contiguous() for t in (values, old_values, returns))
+        for t, name in ((v, "values"), (o, "old_values"), (r, "returns")):
+            L.require_hip_tensor(t, name)
+            if t.dim() != 1 or t.shape != v.shape or t.dtype != torch.float32:
+                raise ValueError("ValueLossClipped: values, old_values and returns (n,) float32")
+        dv = torch.empty_like(v)
+        loss, cf = torch.empty((), device=dev), torch.empty((), device=dev)
+        ws = torch.empty(L.LOSS_WS_DOUBLES, dtype=torch.float64, device=dev)
+        L.check(L.lib.ouz_ppo_value_loss_clipped(v.data_ptr(), o.data_ptr(), r.data_ptr(), v.shape[0], float(clip),
+                                                 ws.data_ptr(), dv.data_ptr(), loss.data_ptr(), cf.data_ptr(),
+                                                 L.stream_ptr(dev)), "ouz_ppo_value_loss_clipped")
+        ctx.save_for_backward(dv)
+        ctx.mark_non_differentiable(cf)
+        ctx.set_materialize_grads(False)
+        return loss, cf
+
+    @staticmethod
+    def backward(ctx, g, _gcf):
+        (dv,) = ctx.saved_tensors
+        return dv * g, None, None, None
+
+
 def policy_sample_ok(hidden, head):
     return (_FUSED_SAMPLE and hidden.is_cuda and not torch.is_grad_enabled() and hidden.dim() == 2
             and hidden.dtype == torch.float32 and hidden.shape[1] % 4 == 0 and head.out_features == L.NUM_ACT

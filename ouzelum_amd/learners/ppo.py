@@ -9,13 +9,16 @@ Differences, all MI355X-side:
 * N and T are parameters: the reference hard-codes ``values.reshape(16, 4096)``
   (``agent.py:61``), so any other env count crashes there.
 * GAE is one HIP launch (``ouz_gae``) instead of a T-step Python loop; values are
-  computed without building an autograd graph (the reference's graph there is
-  never used: ``clip_vloss`` is False).
+  computed without building an autograd graph (the clipped value loss, when ``clip_vloss``
+  asks for it, needs their numbers only).
 * Minibatch permutations come from device RNG (no H2D copy of a numpy permutation) and the clip fractions stay on the device until the end of
   the update (the reference syncs with ``.item()`` every minibatch).
-* The minibatch losses run as HIP kernels on the GPU (``fused.PolicyLoss`` / ``ValueLoss``: forward and input
-  gradients in a handful of launches instead of ~60) whenever they are exactly the loss asked for (ent_coef 0,
-  no clipped value loss; ``OUZ_FUSED_LOSS=0`` keeps the torch form).
+* The minibatch losses run as HIP kernels on the GPU (``fused.PolicyLossEnt`` / ``ValueLoss`` / ``ValueLossClipped``:
+  forward and input gradients in 3 + 2 launches instead of ~60), with or without the update's options (``ent_coef``,
+  ``clip_vloss``); ``OUZ_FUSED_LOSS=0`` keeps the torch form.
+* The update's knobs (``gamma``, ``gae_lambda``, ``clip_coef``, ``norm_adv``, ``ent_coef``, ``vf_coef``,
+  ``clip_vloss``, ``target_kl``, ``max_grad_norm``) are constructor keywords at the reference's values, and
+  ``set_lr_fraction`` anneals the learning rate (``train.py --anneal_lr``).
 * Under torchrun (one process per GPU, env ids sharded) the learner is data
   parallel: rank 0's initial weights are broadcast and every optimizer step
   all-reduces one flattened gradient bucket over RCCL.  The reference learners are
@@ -31,7 +34,7 @@ import torch.distributed as dist
 import torch.nn as nn
 
 from .. import _lib as L
-from .fused import Bf16Shadows, ClipAdam, PolicyLoss, ValueLoss
+from .fused import Bf16Shadows, ClipAdam, PolicyLossEnt, ValueLoss, ValueLossClipped
 from .gemm_tuning import enable_tuned_gemms
 from .models import Critic, LSTMActor, MLPActor
 
@@ -97,11 +100,24 @@ GEMM_DTYPES = ("f32", "bf16")
 
 class PPOLearner:
     def __init__(self, observation_space, action_space, num_envs, device, recurrent=True, rollout_steps=16,
-                 lr=0.0026, num_minibatches=2, update_epochs=4, tuned_gemms=True, rpo_alpha=None, gemm_dtype="f32"):
+                 lr=0.0026, num_minibatches=2, update_epochs=4, tuned_gemms=True, rpo_alpha=None, gemm_dtype="f32",
+                 gamma=0.99, gae_lambda=0.95, clip_coef=0.2, norm_adv=True, ent_coef=0.0, vf_coef=2, clip_vloss=False,
+                 target_kl=None, max_grad_norm=1):
+        """The keywords after ``gemm_dtype`` are the reference update's knobs (agent.py:14-25) at its values; each
+        becomes the attribute of its name (``gae_lambda``: ``gae_lamda``, the reference's spelling), which may also
+        be set after construction."""
         if gemm_dtype not in GEMM_DTYPES:
             raise ValueError(f"gemm_dtype must be one of {GEMM_DTYPES}, not {gemm_dtype!r}")
         if gemm_dtype == "bf16" and torch.device(device).type != "cuda":
             raise ValueError("gemm_dtype='bf16' needs a HIP device: the bf16 GEMM mode has no CPU form")
+        for name, val in (("clip_coef", clip_coef), ("ent_coef", ent_coef), ("lr", lr)):
+            if not val >= 0:
+                raise ValueError(f"{name} must be >= 0, not {val!r}")
+        if target_kl is not None and not target_kl >= 0:
+            raise ValueError(f"target_kl must be None or >= 0, not {target_kl!r}")
+        for name, val in (("gamma", gamma), ("gae_lambda", gae_lambda)):
+            if not 0 <= val <= 1:
+                raise ValueError(f"{name} must lie in [0, 1], not {val!r}")
         self.gemm_dtype = gemm_dtype
         self.obs_dim = observation_space
         self.act_dim = action_space
@@ -109,16 +125,17 @@ class PPOLearner:
         self.rollout_steps = rollout_steps
         self.device = torch.device(device)
         self.recurrent = recurrent
-        self.clip_coef = 0.2
-        self.gamma = 0.99
-        self.gae_lamda = 0.95
-        self.norm_adv = True
+        self.clip_coef = clip_coef
+        self.gamma = gamma
+        self.gae_lamda = gae_lambda
+        self.norm_adv = norm_adv
         self.update_epochs = update_epochs
-        self.ent_coef = 0.0
-        self.vf_coef = 2
-        self.clip_vloss = False
-        self.target_kl = None
-        self.max_grad_norm = 1
+        self.ent_coef = ent_coef
+        self.vf_coef = vf_coef
+        self.clip_vloss = clip_vloss
+        self.target_kl = target_kl
+        self.max_grad_norm = max_grad_norm
+        self.lr0 = lr
         self.num_minibatches = num_minibatches
         self.batch_size = num_envs * rollout_steps
         self.minibatch_size = self.batch_size // num_minibatches
@@ -152,6 +169,13 @@ class PPOLearner:
         sh = self._shadows or (None, None)
         self._clip_adam = ((ClipAdam(self.actor_optimizer, sh[0]), ClipAdam(self.critic_optimizer, sh[1]))
                            if clip_adam else None)
+
+    def set_lr_fraction(self, frac):
+        """Both optimizers' learning rate = ``frac`` * the constructor's ``lr`` (LR annealing: ``train.py --anneal_lr``
+        calls it before each update).  The optimizer step reads the group's ``lr`` on every call."""
+        for opt in (self.actor_optimizer, self.critic_optimizer):
+            for group in opt.param_groups:
+                group["lr"] = frac * self.lr0
 
     def refresh_shadows(self):
         """The bf16 shadows from the current f32 weights, after anything but the optimizer step wrote the weights
@@ -209,16 +233,19 @@ class PPOLearner:
         # the minibatch's four per-row scalars as ONE gather of their stacked rows (each result row contiguous)
         # instead of four (OUZ_STACKED_GATHER=0: one per tensor); exact either way
         scalars = [b_logprobs, b_dones, b_advantages, b_returns]
+        if self.clip_vloss:   # the rollout's values (agent.py:107) as a fifth row of the same gather
+            scalars.append(values.reshape(-1))
         stacked = (torch.stack([x.float() for x in scalars]) if self.device.type == "cuda"
                    and os.environ.get("OUZ_STACKED_GATHER", "1") != "0" else None)
         clipfracs = torch.zeros((), device=self.device)
         n_mb = 0
-        # the HIP loss kernels where they compute exactly the loss asked for: no entropy bonus (ent_coef 0, as both
-        # reference learners) and no clipped value loss; OUZ_FUSED_LOSS=0 keeps the torch form
-        fused_loss = (self.device.type == "cuda" and self.ent_coef == 0 and not self.clip_vloss
-                      and os.environ.get("OUZ_FUSED_LOSS", "1") != "0")
+        # the HIP loss kernels, with or without the entropy bonus and the clipped value loss; OUZ_FUSED_LOSS=0 keeps
+        # the torch form (the yardstick, and the CPU form)
+        fused_loss = self.device.type == "cuda" and os.environ.get("OUZ_FUSED_LOSS", "1") != "0"
         stats = {}
+        epochs_run = 0
         for _ in range(self.update_epochs):
+            epochs_run += 1
             if self.recurrent:
                 envinds = self._perm(N)
                 per = N // self.num_minibatches
@@ -231,23 +258,28 @@ class PPOLearner:
                 mb_state = ((initial_lstm_state[0][:, mbenvinds], initial_lstm_state[1][:, mbenvinds])
                             if self.recurrent else None)
                 if stacked is not None:
-                    mb_logp, mb_done, mb_advs, mb_ret = torch.index_select(stacked, 1, mb_inds).unbind(0)
+                    mb_logp, mb_done, mb_advs, mb_ret, *mb_oldv = torch.index_select(stacked, 1, mb_inds).unbind(0)
                 else:
-                    mb_logp, mb_done, mb_advs, mb_ret = (x[mb_inds] for x in scalars)
+                    mb_logp, mb_done, mb_advs, mb_ret, *mb_oldv = (x[mb_inds] for x in scalars)
                 mb_pomdps, mb_obs = b_pomdps.index_select(0, mb_inds), b_obs.index_select(0, mb_inds)
                 mb_actions = b_actions.index_select(0, mb_inds)
                 if fused_loss:
-                    # the HIP losses (fused.PolicyLoss / ValueLoss): same quantities, ~5 launches instead of ~60
+                    # the HIP losses (fused.PolicyLossEnt / ValueLoss / ValueLossClipped): same quantities, ~5 launches
+                    # instead of ~60
                     mean_z = (self.actor.update_mean(mb_pomdps, mb_state, mb_done) if self.recurrent
                               else self.actor.update_mean(mb_pomdps))
-                    pg_loss, approx_kl, clipfrac = PolicyLoss.apply(
+                    # (with ent_coef 0 the entropy entry's loss and gradients are PolicyLoss's bit for bit, in the same
+                    # three launches; it also reports the entropy)
+                    actor_loss, pg_loss, ent_mean, approx_kl, clipfrac = PolicyLossEnt.apply(
                         mean_z, self.actor.actor_logstd, mb_actions, mb_logp,
-                        mb_advs, self.clip_coef, self.norm_adv)
+                        mb_advs, self.clip_coef, self.norm_adv, self.ent_coef)
                     newvalue = self.critic(mb_obs).view(-1)
-                    v_loss = ValueLoss.apply(newvalue, mb_ret)
+                    if self.clip_vloss:
+                        v_loss, v_clipfrac = ValueLossClipped.apply(newvalue, mb_oldv[0], mb_ret, self.clip_coef)
+                    else:
+                        v_loss = ValueLoss.apply(newvalue, mb_ret)
                     clipfracs += clipfrac
                     n_mb += 1
-                    actor_loss = pg_loss
                 else:
                     if self.recurrent:
                         _, newlogprob, entropy, _ = self.actor(mb_pomdps, mb_state, mb_done,
@@ -266,8 +298,16 @@ class PPOLearner:
                         mb_adv = (mb_adv - mb_adv.mean()) / (mb_adv.std() + 1e-8)
                     pg_loss = torch.max(-mb_adv * ratio,
                                         -mb_adv * torch.clamp(ratio, 1 - self.clip_coef, 1 + self.clip_coef)).mean()
-                    v_loss = 0.5 * ((newvalue - mb_ret) ** 2).mean()
-                    actor_loss = pg_loss - self.ent_coef * entropy.mean()
+                    if self.clip_vloss:   # agent.py:105-114
+                        v_loss_unclipped = (newvalue - mb_ret) ** 2
+                        v_clipped = mb_oldv[0] + torch.clamp(newvalue - mb_oldv[0], -self.clip_coef, self.clip_coef)
+                        v_loss_clipped = (v_clipped - mb_ret) ** 2
+                        v_loss = 0.5 * torch.max(v_loss_unclipped, v_loss_clipped).mean()
+                        v_clipfrac = (v_loss_clipped > v_loss_unclipped).float().mean().detach()
+                    else:
+                        v_loss = 0.5 * ((newvalue - mb_ret) ** 2).mean()
+                    ent_mean = entropy.mean()
+                    actor_loss = pg_loss - self.ent_coef * ent_mean
                 critic_loss = v_loss * self.vf_coef
 
                 self.actor_optimizer.zero_grad()
@@ -279,10 +319,15 @@ class PPOLearner:
                 critic_loss.backward()
                 allreduce_grads(self.critic)
                 self._clip_step(1, self.critic, self.critic_optimizer)
-                stats = {"pg_loss": pg_loss.detach(), "v_loss": v_loss.detach(), "approx_kl": approx_kl}
+                stats = {"pg_loss": pg_loss.detach(), "v_loss": v_loss.detach(), "approx_kl": approx_kl,
+                         "entropy": ent_mean.detach()}
+                if self.clip_vloss:
+                    stats["v_clipfrac"] = v_clipfrac
             if self.target_kl is not None and float(stats["approx_kl"]) > self.target_kl:
                 break
         stats["clipfrac"] = clipfracs / max(n_mb, 1)
+        if self.target_kl is not None:
+            stats["epochs_run"] = epochs_run
         return stats
 
     def _clip_step(self, which, net, optimizer):

@@ -26,6 +26,13 @@ The per-step episode bookkeeping is one ``ouz_episode_step`` launch (``wrappers.
 on the device, and the host reads the count and ``records[:count]`` once per rollout, after the synchronize the
 loop already has.  ``--play`` runs the row's networks from ``--checkpoint``; with ``--learner NAME`` on the
 observations NAME's rollout feeds its policy, logging ``reward/play``.
+
+The update's knobs are flags at the reference's values (``--lr``, ``--update_epochs``, ``--num_minibatches``,
+``--gamma``, ``--gae_lambda``, ``--clip_coef``, ``--vf_coef``, ``--max_grad_norm``, ``--no_norm_adv``, ``--ent_coef``,
+``--clip_vloss``, ``--target_kl``, ``--anneal_lr``, ``--rpo_alpha``); the losses stay on the HIP kernels with any of
+them.  ``--run_tag TAG`` appends ``_TAG`` to the run and checkpoint names, so a tuned run does not overwrite the
+reference-named one.  The new per-update values (``entropy``, ``v_clipfrac``, ``epochs_run``) go to the returned
+history only: the CSV columns and the event tags are the reference's.
 """
 import argparse
 import csv
@@ -72,6 +79,23 @@ def parse_args(argv=None):
                         "accumulation; the rollout and --play stay f32)")
     p.add_argument("--episode_log", default="rollout_mean", choices=["rollout_mean", "per_episode"],
                    help="charts/* points: one mean per rollout, or the reference's one per episode (with --learner)")
+    # the update's knobs (PPOLearner's keywords; defaults: the reference's values, agent.py:14-25); --play ignores them
+    p.add_argument("--lr", type=float, default=0.0026)
+    p.add_argument("--update_epochs", type=int, default=4)
+    p.add_argument("--num_minibatches", type=int, default=2)
+    p.add_argument("--gamma", type=float, default=0.99)
+    p.add_argument("--gae_lambda", type=float, default=0.95)
+    p.add_argument("--clip_coef", type=float, default=0.2)
+    p.add_argument("--vf_coef", type=float, default=2)
+    p.add_argument("--max_grad_norm", type=float, default=1)
+    p.add_argument("--no_norm_adv", action="store_true", help="no advantage normalisation per minibatch")
+    p.add_argument("--ent_coef", type=float, default=0.0, help="entropy bonus (on the HIP loss path)")
+    p.add_argument("--clip_vloss", action="store_true", help="the clipped value loss (on the HIP loss path)")
+    p.add_argument("--target_kl", type=float, default=None, help="stop an update after the epoch whose approx-kl exceeds it")
+    p.add_argument("--anneal_lr", action="store_true", help="lr * (1 - update / num_updates), as CleanRL")
+    p.add_argument("--rpo_alpha", type=float, default=None, help="overrides the learner row's value in training; --play ignores it like the rest of the update's "
+                        "flags, so a policy trained with another alpha plays with the row's value")
+    p.add_argument("--run_tag", default=None, help="appended to the run and checkpoint names (default: the reference's names)")
     args = p.parse_args(argv)
     if args.learner is not None:
         # given explicitly (their defaults say nothing): a second look at the same argv with no defaults
@@ -90,6 +114,28 @@ def parse_args(argv=None):
 def variant_of(args):
     """The table row the flags select: ``--learner``'s, or the one ``--algo`` / ``--rollout_obs`` describe."""
     return VARIANTS[args.learner] if args.learner is not None else legacy_variant(args.algo, args.rollout_obs)
+
+
+def learner_kwargs(args, v):
+    """PPOLearner's update keywords from the flags; ``--rpo_alpha`` overrides the row's value."""
+    return {"lr": args.lr, "update_epochs": args.update_epochs, "num_minibatches": args.num_minibatches,
+            "gamma": args.gamma, "gae_lambda": args.gae_lambda, "clip_coef": args.clip_coef, "vf_coef": args.vf_coef,
+            "max_grad_norm": args.max_grad_norm, "norm_adv": not args.no_norm_adv, "ent_coef": args.ent_coef,
+            "clip_vloss": args.clip_vloss, "target_kl": args.target_kl,
+            "rpo_alpha": v.rpo_alpha if args.rpo_alpha is None else args.rpo_alpha}
+
+
+def run_names(args, v):
+    """(run, best checkpoint) names: the reference's (variants.names), with ``--run_tag`` appended when given."""
+    name, best = names(v, args.POMDP, args.pomdp_prob)
+    if args.run_tag:
+        name, best = f"{name}_{args.run_tag}", f"{best}_{args.run_tag}"
+    return name, best
+
+
+def annealed_fraction(update_index, num_updates):
+    """``--anneal_lr``: the learning-rate fraction before update ``update_index`` (from 0) of ``num_updates``."""
+    return 1.0 - update_index / num_updates
 
 
 def write_episode_points(tb, records, g0, step_envs):
@@ -213,8 +259,9 @@ def train(args, on_rollout=None):
     envs = EpisodeRecorder(ExtractObsWrapper(base), device, env_id0=off, capacity=3 * N)
     pomdp_w = POMDPWrapper(args.POMDP, args.pomdp_prob, seed=args.seed + 1, row_offset=off)
     agent = PPOLearner(base.observation_space, base.action_space, N, device, recurrent=v.recurrent,
-                       rollout_steps=T, rpo_alpha=v.rpo_alpha, gemm_dtype=args.gemm_dtype)
-    name, best = names(v, args.POMDP, args.pomdp_prob)
+                       rollout_steps=T, gemm_dtype=args.gemm_dtype, **learner_kwargs(args, v))
+    name, best = run_names(args, v)
+    num_updates = max(1, -(-args.total_steps // (T * N * world)))   # the loop's trips
     ro = Rollout(envs, pomdp_w, agent, v, T, watch=on_rollout is not None)
 
     writer = tb = None
@@ -234,6 +281,8 @@ def train(args, on_rollout=None):
         g0 = global_step
         ro.collect(per_episode)
         global_step += T * N * world
+        if args.anneal_lr:
+            agent.set_lr_fraction(annealed_fraction(len(history), num_updates))
         stats = ro.update()
         ep = base.episode_stats()
         mean_rew = ro.rewards.mean()

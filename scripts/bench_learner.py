@@ -5,6 +5,7 @@ PPO update of 4 epochs x 2 minibatches) and splits wall time into rollout and up
     python scripts/bench_learner.py --env Landing --num_envs 4096 --iters 20
     python scripts/bench_learner.py --env QuadFault --num_envs 8192 --learner RPO-LSTM [--episode_log per_episode]
     python scripts/bench_learner.py --env QuadFault --num_envs 8192 --gemm_dtype bf16
+    python scripts/bench_learner.py --env QuadFault --num_envs 8192 --ent_coef 0.01 --clip_vloss
 
 The rollout is train.py's (``learners.train.Rollout``).  ``--algo`` times it on the bare env, with no episode
 bookkeeping; ``--learner NAME`` in NAME's routing (learners/variants.py) with the bookkeeping train.py has, one
@@ -35,6 +36,10 @@ ap.add_argument("--warmup", type=int, default=3)
 ap.add_argument("--learner", default=None, choices=list(LEARNERS))
 ap.add_argument("--episode_log", default="rollout_mean", choices=["rollout_mean", "per_episode"])
 ap.add_argument("--gemm_dtype", default="f32", choices=["f32", "bf16"])
+ap.add_argument("--ent_coef", type=float, default=0.0)
+ap.add_argument("--clip_vloss", action="store_true")
+ap.add_argument("--update_epochs", type=int, default=4)
+ap.add_argument("--num_minibatches", type=int, default=2)
 a = ap.parse_args()
 v = VARIANTS[a.learner] if a.learner else legacy_variant(a.algo, "clean")
 per_episode = a.learner is not None and a.episode_log == "per_episode"
@@ -46,7 +51,10 @@ env = ExtractObsWrapper(base)
 if a.learner:
     env = EpisodeRecorder(env, dev, capacity=3 * N)
 agent = PPOLearner(base.observation_space, base.action_space, N, dev, recurrent=v.recurrent, rpo_alpha=v.rpo_alpha,
-                   gemm_dtype=a.gemm_dtype)
+                   gemm_dtype=a.gemm_dtype, ent_coef=a.ent_coef, clip_vloss=a.clip_vloss,
+                   update_epochs=a.update_epochs, num_minibatches=a.num_minibatches)
+options = {k: getattr(a, k) for k, d in (("ent_coef", 0.0), ("clip_vloss", False), ("update_epochs", 4),
+                                         ("num_minibatches", 2)) if getattr(a, k) != d}   # the ones given
 ro = Rollout(env, POMDPWrapper("flicker", 0.1, seed=1), agent, v, T)
 t_roll = t_upd = 0.0
 n_records = 0
@@ -69,7 +77,7 @@ for it in range(a.warmup + a.iters):
 steps = N * T * a.iters
 print(json.dumps({"algo": a.algo, **({"learner": a.learner, "episode_log": a.episode_log,
                                       "records": n_records} if a.learner else {}), "env": a.env, "num_envs": N,
-                  "iters": a.iters, "gemm_dtype": a.gemm_dtype,
+                  "iters": a.iters, "gemm_dtype": a.gemm_dtype, **options,
                   "train_env_steps_per_s": round(steps / (t_roll + t_upd), 1),
                   "rollout_env_steps_per_s": round(steps / t_roll, 1),
                   "rollout_ms_per_iter": round(t_roll / a.iters * 1e3, 3),
