@@ -76,7 +76,9 @@ extern "C" {
                                8: the learner's bf16 GEMM mode (ouz_linear_tanh_small_k_bf16, ouz_tanh_bwd_bias_bf16,
                                   ouz_adam_clip_step_shadow);
                                9: the PPO update's options on the loss kernels (ouz_ppo_policy_loss_ent: entropy
-                                  bonus; ouz_ppo_value_loss_clipped: clipped value loss) */
+                                  bonus; ouz_ppo_value_loss_clipped: clipped value loss); entry points added since
+                                  with no struct or signature changed: the running normalisation (ouz_moments_batch,
+                                  ouz_moments_merge, ouz_normalize_rows, ouz_linear_tanh_small_k_norm) */
 
 /* error codes */
 #define OUZ_OK 0
@@ -472,6 +474,45 @@ int ouz_linear_tanh_small_k(const float* x, const float* w, const float* b, int3
  * consecutive outputs (16 bytes) where cols >= 8, four (8 bytes) at cols = 4. */
 int ouz_linear_tanh_small_k_bf16(const float* x, const float* w, const float* b, int32_t rows, int32_t K,
                                  int32_t cols, uint16_t* y, void* stream);
+
+/* Running normalisation of the learner's inputs and value targets (entry points added under ABI 9).  A normaliser
+ * over d columns, 1 <= d <= OUZ_NORM_MAX_D, keeps in f64 device memory mean [d], the population variance var [d]
+ * and one count (initially 0, 1 and 1), and in f32 the constants every f32 path reads: m [d] = (float)mean and
+ * r [d] = (float)(1 / sqrt(var + eps)).  All f32 row buffers are row-major and contiguous.  Every operation below
+ * is rounded once (no multiply-add contraction); nothing uses floating-point atomics, so results are the same bits
+ * on every run.
+ *
+ * ouz_moments_batch: the triple of a batch x [rows][d], rows >= 1: out [2 d + 1] = n, mean [d], M2 [d] (the sums
+ * of squared deviations from the batch mean), f64.  Two launches: a fixed grid of OUZ_MOMENTS_BLOCKS blocks, each
+ * reducing a contiguous slice of rows per column in two passes (the mean, then the deviations from it), and one
+ * block that merges the block partials in block order with Chan's update.  workspace: OUZ_MOMENTS_WS_DOUBLES
+ * doubles of device memory, not kept between calls.
+ *
+ * ouz_moments_merge: merges parts [n_parts][2 d + 1] (triples in ouz_moments_batch's layout), in order, into the
+ * running statistics in place; for each triple (n, bmean, bM2):
+ *   delta = bmean - mean, tot = count + n, mean' = mean + delta n / tot,
+ *   M2' = var count + bM2 + delta^2 count n / tot, var' = M2' / tot, count' = tot;
+ * then writes m and r.  One launch.
+ *
+ * ouz_normalize_rows: mode OUZ_NORM_FORWARD: out = clamp((in - m) r, -clip, clip), clip > 0 (+inf: no clip), a NaN
+ * input gives a NaN output as torch.clamp does; mode OUZ_NORM_INVERSE: out = in / r + m (the quotient correctly
+ * rounded; clip unused).  in and out [rows][d]; in == out is allowed.  One launch.
+ *
+ * ouz_linear_tanh_small_k_norm: ouz_linear_tanh_small_k with the forward normalisation as its load prologue,
+ * y = tanh(W norm(x) + b); bit for bit the result of ouz_normalize_rows followed by ouz_linear_tanh_small_k.  Forward
+ * only: the learner's calls without autograd (the rollout policy, the value pass, play). */
+#define OUZ_NORM_MAX_D 16
+#define OUZ_MOMENTS_BLOCKS 256
+#define OUZ_MOMENTS_WS_DOUBLES (33 * OUZ_MOMENTS_BLOCKS)
+#define OUZ_NORM_FORWARD 0
+#define OUZ_NORM_INVERSE 1
+int ouz_moments_batch(const float* x, int32_t rows, int32_t d, double* workspace, double* out, void* stream);
+int ouz_moments_merge(const double* parts, int32_t n_parts, int32_t d, double eps, double* mean, double* var,
+                      double* count, float* m, float* r, void* stream);
+int ouz_normalize_rows(const float* in, const float* m, const float* r, int32_t rows, int32_t d, float clip, int32_t mode,
+                       float* out, void* stream);
+int ouz_linear_tanh_small_k_norm(const float* x, const float* m, const float* r, float clip, const float* w,
+                                 const float* b, int32_t rows, int32_t K, int32_t cols, float* y, void* stream);
 
 /* Gradient-norm clipping + Adam over one network's parameter tensors in two launches (RPO-LSTM/agent.py:124-134:
  * nn.utils.clip_grad_norm_(params, max_norm) then torch.optim.Adam.step(); torch/optim/adam.py single-tensor order).

@@ -180,9 +180,17 @@ SIGNATURES = {
     "ouz_adam_clip_step_shadow": (_I, [ctypes.POINTER(OuzAdamTable), ctypes.POINTER(OuzAdamShadows), ctypes.c_double,
                                        ctypes.c_double, ctypes.c_double, ctypes.c_double, _I64, ctypes.c_double, _P,
                                        _P]),
+    "ouz_moments_batch": (_I, [_P, _I, _I, _P, _P, _P]),
+    "ouz_moments_merge": (_I, [_P, _I, _I, ctypes.c_double, _P, _P, _P, _P, _P, _P]),
+    "ouz_normalize_rows": (_I, [_P, _P, _P, _I, _I, _F, _I, _P, _P]),
+    "ouz_linear_tanh_small_k_norm": (_I, [_P, _P, _P, _F, _P, _P, _I, _I, _I, _P, _P]),
 }
 LOSS_WS_DOUBLES = 10 * 256      # OUZ_LOSS_WS_DOUBLES
 COLSUM_BLOCKS = 1024            # OUZ_COLSUM_BLOCKS
+NORM_MAX_D = 16                 # OUZ_NORM_MAX_D
+MOMENTS_BLOCKS = 256            # OUZ_MOMENTS_BLOCKS
+MOMENTS_WS_DOUBLES = 33 * 256   # OUZ_MOMENTS_WS_DOUBLES
+NORM_FORWARD, NORM_INVERSE = 0, 1
 
 
 # include/ouzelum_host.h, the same way: this table IS the list of symbols that header declares.

@@ -1028,6 +1028,153 @@ __global__ void __launch_bounds__(256) adam_step_kernel(ouz_adam_table t, ouz_ad
 }
 
 // ---------------------------------------------------------------------------
+// Running normalisation of the learner's inputs and value targets (PPOLearner(normalize_input, normalize_value);
+// DESIGN.md §9.2).  The statistics (mean, population variance, count) live in f64 on the device; what the f32 paths
+// read are m = (float)mean and r = (float)(1 / sqrt(var + eps)), rewritten in place by every merge.
+//  * moments_block_kernel + moments_finish_kernel (ouz_moments_batch): (n, mean, M2) of a (rows, d) batch.  A fixed
+//    grid of OUZ_MOMENTS_BLOCKS blocks; a block owns a contiguous slice of rows and reads it as one flat array with a
+//    thread stride that is a multiple of d, so a thread stays on one column and the loads are coalesced.  Two passes
+//    over the slice in f64 (the mean, then the squared deviations from it with the usual first-order correction);
+//    one thread per column then merges the block partials in block order with Chan's update.  No atomics: the
+//    result is the same bits on every run.
+//  * moments_merge_kernel (ouz_moments_merge): Chan's update of the running statistics by n_parts batch triples, in
+//    order, and the derived m / r.
+//  * normalize_rows_kernel (ouz_normalize_rows): y = clamp((x - m) r, -clip, clip), or the inverse x = y / r + m.
+// Every operation is rounded once (no contraction), so the torch form (fused.RunningNorm) is the same arithmetic.
+// ---------------------------------------------------------------------------
+constexpr int kNormMaxD = OUZ_NORM_MAX_D;
+constexpr int kMomBlocks = OUZ_MOMENTS_BLOCKS;
+constexpr int kMomStride = 2 * kNormMaxD + 1;   // doubles per block partial: n, mean[16], M2[16]
+static_assert(OUZ_MOMENTS_WS_DOUBLES == kMomBlocks * kMomStride, "workspace: one partial per block");
+
+// clamp((x - m) * r, -clip, clip) as torch forms it: a NaN fails both comparisons and passes through, clip = +inf
+// clips nothing
+__device__ __forceinline__ float norm_forward(float x, float m, float r, float clip) {
+#pragma clang fp contract(off)
+  float y = (x - m) * r;
+  y = y < -clip ? -clip : y;
+  y = y > clip ? clip : y;
+  return y;
+}
+
+__global__ void __launch_bounds__(256) moments_block_kernel(const float* __restrict__ x, int rows, int d,
+                                                            double* __restrict__ part) {
+#pragma clang fp contract(off)
+  __shared__ double sh1[256], sh2[256], smean[kNormMaxD];
+  const int per = (rows + kMomBlocks - 1) / kMomBlocks;
+  const long long lo = (long long)blockIdx.x * per, hi = lo + per;
+  const int r0 = (int)(lo < rows ? lo : rows), r1 = (int)(hi < rows ? hi : rows);
+  const int nb = r1 - r0;
+  const int stride = (256 / d) * d;   // a multiple of d: thread t reads column t % d only
+  const int tid = threadIdx.x, col = tid % d;
+  const float* xb = x + (size_t)r0 * d;
+  const size_t ne = tid < stride ? (size_t)nb * d : 0;
+  double s = 0.0;
+  for (size_t e = tid; e < ne; e += stride) s += (double)xb[e];
+  sh1[tid] = s;
+  __syncthreads();
+  if (tid < d) {   // the column's threads, in thread order
+    double t = 0.0;
+    for (int q = tid; q < stride; q += d) t += sh1[q];
+    smean[tid] = nb > 0 ? t / (double)nb : 0.0;
+  }
+  __syncthreads();
+  const double mu = smean[col];
+  double q1 = 0.0, q2 = 0.0;
+  for (size_t e = tid; e < ne; e += stride) {
+    const double dv = (double)xb[e] - mu;
+    q1 += dv;
+    q2 += dv * dv;
+  }
+  sh1[tid] = q1;
+  sh2[tid] = q2;
+  __syncthreads();
+  if (tid < d) {
+    double t1 = 0.0, t2 = 0.0;
+    for (int q = tid; q < stride; q += d) {
+      t1 += sh1[q];
+      t2 += sh2[q];
+    }
+    // sum (x - mu)^2 - (sum (x - mu))^2 / n: the second term is the rounding of mu, squared (zero for one row)
+    const double m2 = nb > 0 ? t2 - t1 * t1 / (double)nb : 0.0;
+    double* p = part + (size_t)blockIdx.x * kMomStride;
+    if (tid == 0) p[0] = (double)nb;
+    p[1 + tid] = mu;
+    p[1 + kNormMaxD + tid] = m2 > 0.0 ? m2 : 0.0;
+  }
+}
+
+// One thread per column: Chan's merge of the block partials in block order.  The means enter shifted by block 0's
+// (the merge commutes with a shift), so the running mean rounds at the scale of the deviations, not of the mean.
+__global__ void __launch_bounds__(64) moments_finish_kernel(const double* __restrict__ part, int d,
+                                                            double* __restrict__ out) {
+#pragma clang fp contract(off)
+  const int c = threadIdx.x;
+  if (c >= d) return;
+  const double shift = part[1 + c];
+  double n = 0.0, mean = 0.0, m2 = 0.0;
+  for (int b = 0; b < kMomBlocks; ++b) {
+    const double* p = part + (size_t)b * kMomStride;
+    const double nb = p[0];
+    if (nb == 0.0) continue;   // a block past the last row
+    const double delta = (p[1 + c] - shift) - mean;
+    const double tot = n + nb;
+    mean = mean + delta * nb / tot;
+    m2 = m2 + p[1 + kNormMaxD + c] + delta * delta * n * nb / tot;
+    n = tot;
+  }
+  if (c == 0) out[0] = n;
+  out[1 + c] = shift + mean;
+  out[1 + d + c] = m2;
+}
+
+__global__ void __launch_bounds__(64) moments_merge_kernel(const double* __restrict__ parts, int n_parts, int d,
+                                                           double eps, double* __restrict__ mean,
+                                                           double* __restrict__ var, double* __restrict__ count,
+                                                           float* __restrict__ m, float* __restrict__ r) {
+#pragma clang fp contract(off)
+  const int c = threadIdx.x;
+  double cnt = *count;   // read by every thread before thread 0 rewrites it
+  __syncthreads();
+  if (c >= d) return;
+  double mu = mean[c], v = var[c];
+  for (int k = 0; k < n_parts; ++k) {
+    const double* p = parts + (size_t)k * (2 * d + 1);
+    const double n = p[0];
+    const double delta = p[1 + c] - mu;
+    const double tot = cnt + n;
+    mu = mu + delta * n / tot;
+    const double m2 = v * cnt + p[1 + d + c] + delta * delta * cnt * n / tot;
+    v = m2 / tot;
+    cnt = tot;
+  }
+  mean[c] = mu;
+  var[c] = v;
+  if (c == 0) *count = cnt;
+  m[c] = (float)mu;
+  r[c] = (float)(1.0 / sqrt(v + eps));
+}
+
+// in and out may be the same buffer (each element is read and written by one thread), so neither is __restrict__.
+// The inverse's quotient is formed in f64 and rounded once: the correctly rounded f32 quotient (53 >= 2 * 24 + 2
+// bits), whatever the build's f32 division is.
+__global__ void __launch_bounds__(256) normalize_rows_kernel(const float* in, const float* __restrict__ m,
+                                                             const float* __restrict__ r, size_t n, int d, float clip,
+                                                             int inverse, float* out) {
+#pragma clang fp contract(off)
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+    const int c = (int)(i % (size_t)d);
+    const float x = in[i];
+    if (inverse) {
+      const float q = (float)((double)x / (double)r[c]);
+      out[i] = q + m[c];
+    } else {
+      out[i] = norm_forward(x, m[c], r[c], clip);
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
 // The trunks' first layer, y = tanh(x W^T + b) with K <= 16 inputs (the 13 observations; RPO-LSTM/model.py:11-20,
 // agent.py critic), in ONE pass: hipBLASLt's K = 13 GEMM writes the pre-activation and torch's tanh reads and rewrites
 // it, where this layer is a write of y and nothing else.  W^T, b and a chunk of rows' inputs sit in LDS; each thread
@@ -1042,10 +1189,17 @@ constexpr int kSmallKChunk = 64;   // at most this many rows' inputs staged in L
 // OutT float: W = 4.  OutT uint16_t (ouz_linear_tanh_small_k_bf16): the same staging and f32 arithmetic, each output
 // rounded to bf16 once at the store, W = 8 consecutive outputs of a row per thread (one 16-byte store) or, at
 // cols = 4, W = 4 (8 bytes).
-template <typename OutT, int W>
+//
+// NORM (ouz_linear_tanh_small_k_norm): the running normaliser as the load prologue.  Each input goes through
+// norm_forward (ouz_normalize_rows' arithmetic) on its way into LDS and the sums below are the same code, so the
+// result is bit for bit that of ouz_normalize_rows followed by ouz_linear_tanh_small_k.
+template <typename OutT, int W, bool NORM = false>
 __global__ void __launch_bounds__(256) linear_tanh_smallk_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                                  const float* __restrict__ b, int rows, int K, int cols,
-                                                                 int chunk, OutT* __restrict__ y) {
+                                                                 int chunk, OutT* __restrict__ y,
+                                                                 const float* __restrict__ norm_m = nullptr,
+                                                                 const float* __restrict__ norm_r = nullptr,
+                                                                 float norm_clip = 0.0f) {
   extern __shared__ float sw[];   // W^T [K][cols], b [cols], then the chunk's inputs [chunk][K]
   float* sx = sw + (K + 1) * cols;
   for (int e = threadIdx.x; e < K * cols; e += 256) {
@@ -1060,7 +1214,15 @@ __global__ void __launch_bounds__(256) linear_tanh_smallk_kernel(const float* __
   for (int r0 = blockIdx.x * chunk; r0 < rows; r0 += gridDim.x * chunk) {
     const int nr = rows - r0 < chunk ? rows - r0 : chunk;
     __syncthreads();   // W^T / b written (first chunk), every thread done with the previous chunk's inputs
-    for (int e = threadIdx.x; e < nr * K; e += 256) sx[e] = x[(size_t)r0 * K + e];
+    for (int e = threadIdx.x; e < nr * K; e += 256) {
+      const float xv = x[(size_t)r0 * K + e];
+      if constexpr (NORM) {
+        const int k = e % K;   // a chunk starts on a row boundary
+        sx[e] = norm_forward(xv, norm_m[k], norm_r[k], norm_clip);
+      } else {
+        sx[e] = xv;
+      }
+    }
     __syncthreads();
     f32x4 bias[W / 4];
 #pragma unroll
@@ -1443,10 +1605,12 @@ int ouz_adam_clip_step_shadow(const ouz_adam_table* t, const ouz_adam_shadows* s
 
 
 extern "C++" {
-// ouz_linear_tanh_small_k (OutT float) and ouz_linear_tanh_small_k_bf16 (OutT uint16_t)
+// ouz_linear_tanh_small_k (OutT float), ouz_linear_tanh_small_k_bf16 (OutT uint16_t) and, with a normaliser's m / r
+// (f32 output only), ouz_linear_tanh_small_k_norm
 template <typename OutT>
 static int linear_tanh_small_k(const char* name, const float* x, const float* w, const float* b, int32_t rows, int32_t K,
-                               int32_t cols, OutT* y, void* stream) {
+                               int32_t cols, OutT* y, void* stream, const float* m = nullptr, const float* r = nullptr,
+                               float clip = 0.0f) {
   const std::string n(name);
   if (rows < 0 || K < 1 || K > kSmallKMax || cols < 4 || cols > 1024 || (cols & (cols - 1)))
     return set_error(OUZ_ERR_INVALID, n + ": rows >= 0, 1 <= K <= 16, cols a power of two in [4, 1024]");
@@ -1458,18 +1622,66 @@ static int linear_tanh_small_k(const char* name, const float* x, const float* w,
   const int blocks = std::min((rows + chunk - 1) / chunk, kSmallKBlocks);
   const size_t lds = ((size_t)(K + 1) * cols + (size_t)chunk * K) * sizeof(float);
   const hipStream_t s = (hipStream_t)stream;
-  if constexpr (sizeof(OutT) == 4)
-    hipLaunchKernelGGL((linear_tanh_smallk_kernel<float, 4>), dim3(blocks), dim3(256), lds, s, x, w, b, rows, K, cols,
-                       chunk, y);
-  else if (cols >= 8)
+  const float* none = nullptr;
+  if constexpr (sizeof(OutT) == 4) {
+    if (m)
+      hipLaunchKernelGGL((linear_tanh_smallk_kernel<float, 4, true>), dim3(blocks), dim3(256), lds, s, x, w, b, rows, K,
+                         cols, chunk, y, m, r, clip);
+    else
+      hipLaunchKernelGGL((linear_tanh_smallk_kernel<float, 4>), dim3(blocks), dim3(256), lds, s, x, w, b, rows, K, cols,
+                         chunk, y, none, none, 0.0f);
+  } else if (cols >= 8) {
     hipLaunchKernelGGL((linear_tanh_smallk_kernel<uint16_t, 8>), dim3(blocks), dim3(256), lds, s, x, w, b, rows, K, cols,
-                       chunk, y);
-  else
+                       chunk, y, none, none, 0.0f);
+  } else {
     hipLaunchKernelGGL((linear_tanh_smallk_kernel<uint16_t, 4>), dim3(blocks), dim3(256), lds, s, x, w, b, rows, K, cols,
-                       chunk, y);
+                       chunk, y, none, none, 0.0f);
+  }
   return launch_status("linear_tanh_smallk_kernel");
 }
 }  // extern "C++"
+
+int ouz_moments_batch(const float* x, int32_t rows, int32_t d, double* workspace, double* out, void* stream) {
+  if (rows < 1 || d < 1 || d > kNormMaxD)
+    return set_error(OUZ_ERR_INVALID, "ouz_moments_batch: rows >= 1 and 1 <= d <= 16");
+  if (!x || !workspace || !out) return set_error(OUZ_ERR_INVALID, "ouz_moments_batch: null buffer");
+  const hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(moments_block_kernel, dim3(kMomBlocks), dim3(256), 0, s, x, rows, d, workspace);
+  hipLaunchKernelGGL(moments_finish_kernel, dim3(1), dim3(64), 0, s, workspace, d, out);
+  return launch_status("moments_block_kernel");
+}
+
+int ouz_moments_merge(const double* parts, int32_t n_parts, int32_t d, double eps, double* mean, double* var,
+                      double* count, float* m, float* r, void* stream) {
+  if (n_parts < 1 || d < 1 || d > kNormMaxD || !(eps >= 0.0))
+    return set_error(OUZ_ERR_INVALID, "ouz_moments_merge: n_parts >= 1, 1 <= d <= 16 and eps >= 0");
+  if (!parts || !mean || !var || !count || !m || !r) return set_error(OUZ_ERR_INVALID, "ouz_moments_merge: null buffer");
+  hipLaunchKernelGGL(moments_merge_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, parts, n_parts, d, eps, mean, var,
+                     count, m, r);
+  return launch_status("moments_merge_kernel");
+}
+
+int ouz_normalize_rows(const float* in, const float* m, const float* r, int32_t rows, int32_t d, float clip, int32_t mode,
+                       float* out, void* stream) {
+  if (rows < 0 || d < 1 || d > kNormMaxD) return set_error(OUZ_ERR_INVALID, "ouz_normalize_rows: rows >= 0 and 1 <= d <= 16");
+  if (mode != OUZ_NORM_FORWARD && mode != OUZ_NORM_INVERSE)
+    return set_error(OUZ_ERR_INVALID, "ouz_normalize_rows: mode is OUZ_NORM_FORWARD or OUZ_NORM_INVERSE");
+  if (mode == OUZ_NORM_FORWARD && !(clip > 0.0f)) return set_error(OUZ_ERR_INVALID, "ouz_normalize_rows: clip must be > 0");
+  if (rows == 0) return OUZ_OK;   // (torch's empty tensors have null data pointers)
+  if (!in || !m || !r || !out) return set_error(OUZ_ERR_INVALID, "ouz_normalize_rows: null buffer");
+  const size_t n = (size_t)rows * d;
+  const int blocks = (int)std::min<size_t>((n + 255) / 256, 1024);
+  hipLaunchKernelGGL(normalize_rows_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, in, m, r, n, d, clip,
+                     mode == OUZ_NORM_INVERSE ? 1 : 0, out);
+  return launch_status("normalize_rows_kernel");
+}
+
+int ouz_linear_tanh_small_k_norm(const float* x, const float* m, const float* r, float clip, const float* w,
+                                 const float* b, int32_t rows, int32_t K, int32_t cols, float* y, void* stream) {
+  if (!(clip > 0.0f)) return set_error(OUZ_ERR_INVALID, "ouz_linear_tanh_small_k_norm: clip must be > 0");
+  if (rows > 0 && (!m || !r)) return set_error(OUZ_ERR_INVALID, "ouz_linear_tanh_small_k_norm: null buffer");
+  return linear_tanh_small_k("ouz_linear_tanh_small_k_norm", x, w, b, rows, K, cols, y, stream, m, r, clip);
+}
 
 int ouz_linear_tanh_small_k(const float* x, const float* w, const float* b, int32_t rows, int32_t K, int32_t cols,
                             float* y, void* stream) {

@@ -23,6 +23,7 @@
 import os
 
 import torch
+import torch.distributed as dist
 
 from .. import _lib as L
 
@@ -94,6 +95,156 @@ def linear_tanh_small_k(x, weight, bias):
     y = torch.empty((x.shape[0], w.shape[0]), device=x.device)
     L.check(L.lib.ouz_linear_tanh_small_k(x.data_ptr(), w.data_ptr(), b.data_ptr(), x.shape[0], w.shape[1], w.shape[0],
                                           y.data_ptr(), L.stream_ptr(x.device)), "ouz_linear_tanh_small_k")
+    return y
+
+
+def _fused_norm(t):
+    """The HIP kernels of the running normalisation apply: a tensor on the GPU and not ``OUZ_FUSED_NORM=0`` (read at
+    call time, as ``OUZ_FUSED_LOSS`` is: the torch form is the yardstick, and the CPU form)."""
+    return t.is_cuda and os.environ.get("OUZ_FUSED_NORM", "1") != "0"
+
+
+def _world():
+    return dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
+
+
+class RunningNorm:
+    """Running mean / variance normalisation of ``d`` columns (``PPOLearner(normalize_input,
+    normalize_value)``).  The statistics live in one f64 device tensor ``state`` = [mean (d), var (d), count]
+    (population variance; 0, 1, 1 at the start); the f32 paths read ``m`` = (float)mean and ``r`` =
+    (float)(1 / sqrt(var + eps)).  ``state``, ``m`` and ``r`` are updated IN PLACE by every merge, so a captured
+    hipGraph that reads ``m`` / ``r`` sees the current statistics on every replay.
+
+    ``normalize``: y = clamp((x - m) * r, -clip, clip) in f32, each operation rounded once (``clip`` None: no clip);
+    ``denormalize``: x = y / r + m.  ``update(x)``: the batch triple (n, mean, M2) of the (rows, d) f32 ``x``, one
+    all-gather of the 2 d + 1 doubles under data parallelism, and Chan's merge of every rank's triple in rank order
+    (all ranks end with the same bits).  On the GPU these are ``ouz_normalize_rows``, ``ouz_moments_batch`` and
+    ``ouz_moments_merge``; on CPU tensors, or with ``OUZ_FUSED_NORM=0``, the same formulas as torch operations."""
+
+    def __init__(self, d, device, clip=None, eps=1e-5):
+        if not 1 <= d <= L.NORM_MAX_D:
+            raise ValueError(f"RunningNorm: 1 <= d <= {L.NORM_MAX_D}, not {d}")
+        if clip is not None and not clip > 0:
+            raise ValueError(f"RunningNorm: clip must be None or > 0, not {clip!r}")
+        self.d, self.eps = d, float(eps)
+        self.clip = float("inf") if clip is None else float(clip)
+        self.device = torch.device(device)
+        self.state = torch.zeros(2 * d + 1, dtype=torch.float64, device=self.device)
+        self.state[d:] = 1.0
+        self.mean, self.var, self.count = self.state[:d], self.state[d:2 * d], self.state[2 * d:]   # views
+        self.m = torch.empty(d, device=self.device)
+        self.r = torch.empty(d, device=self.device)
+        self._ws = (torch.empty(L.MOMENTS_WS_DOUBLES, dtype=torch.float64, device=self.device)
+                    if self.device.type == "cuda" else None)
+        self.derive()
+
+    @torch.no_grad()
+    def derive(self):
+        """m and r from the f64 statistics (after ``load_state``; every merge ends with it)."""
+        self.m.copy_(self.mean)
+        self.r.copy_(1.0 / torch.sqrt(self.var + self.eps))
+
+    def _rows(self, x, name):
+        if x.dim() != 2 or x.shape[1] != self.d or x.dtype != torch.float32:
+            raise ValueError(f"RunningNorm.{name}: a (rows, {self.d}) float32 tensor, not {tuple(x.shape)} {x.dtype}")
+        return x.contiguous()
+
+    def _normalize_rows(self, x, mode, out):
+        out = torch.empty_like(x) if out is None else out
+        if out.shape != x.shape or out.dtype != x.dtype or not out.is_contiguous():
+            raise ValueError("RunningNorm: out must be a contiguous tensor of the input's shape and dtype")
+        L.check(L.lib.ouz_normalize_rows(x.data_ptr(), self.m.data_ptr(), self.r.data_ptr(), x.shape[0], self.d,
+                                         self.clip, mode, out.data_ptr(), L.stream_ptr(x.device)),
+                "ouz_normalize_rows")
+        return out
+
+    @torch.no_grad()
+    def normalize(self, x, out=None):
+        """clamp((x - m) * r, -clip, clip) of (rows, d) f32 rows; ``out`` may be ``x`` itself."""
+        x = self._rows(x, "normalize")
+        if _fused_norm(x):
+            return self._normalize_rows(x, L.NORM_FORWARD, out)
+        return torch.clamp((x - self.m) * self.r, -self.clip, self.clip, out=out)
+
+    @torch.no_grad()
+    def denormalize(self, y, out=None):
+        """y / r + m of (rows, d) f32 rows; ``out`` may be ``y`` itself."""
+        y = self._rows(y, "denormalize")
+        if _fused_norm(y):
+            return self._normalize_rows(y, L.NORM_INVERSE, out)
+        return torch.add(y / self.r, self.m, out=out)
+
+    @torch.no_grad()
+    def batch_moments(self, x):
+        """[n, mean (d), M2 (d)] of the rows, f64: M2 the sums of squared deviations from the batch mean."""
+        x = self._rows(x, "batch_moments")
+        if x.shape[0] < 1:
+            raise ValueError("RunningNorm.batch_moments: at least one row")
+        out = torch.empty(2 * self.d + 1, dtype=torch.float64, device=x.device)
+        if _fused_norm(x):
+            L.check(L.lib.ouz_moments_batch(x.data_ptr(), x.shape[0], self.d, self._ws.data_ptr(), out.data_ptr(),
+                                            L.stream_ptr(x.device)), "ouz_moments_batch")
+            return out
+        x64 = x.double()
+        mean = x64.mean(0)
+        out[0] = x.shape[0]
+        out[1:1 + self.d] = mean
+        out[1 + self.d:] = (x64 - mean).square().sum(0)
+        return out
+
+    @torch.no_grad()
+    def merge(self, parts):
+        """Chan's merge of ``parts`` (n_parts, 2 d + 1) f64 triples, in order, into the statistics; then m and r."""
+        d = self.d
+        parts = parts.reshape(-1, 2 * d + 1).contiguous()
+        if parts.dtype != torch.float64 or parts.device != self.state.device or parts.shape[0] < 1:
+            raise ValueError("RunningNorm.merge: (n_parts, 2 d + 1) float64 triples on the normaliser's device")
+        if _fused_norm(parts):
+            L.check(L.lib.ouz_moments_merge(parts.data_ptr(), parts.shape[0], d, self.eps, self.mean.data_ptr(),
+                                            self.var.data_ptr(), self.count.data_ptr(), self.m.data_ptr(),
+                                            self.r.data_ptr(), L.stream_ptr(parts.device)), "ouz_moments_merge")
+            return
+        for p in parts:
+            n, bmean, bm2 = p[0], p[1:1 + d], p[1 + d:]
+            delta = bmean - self.mean
+            tot = self.count + n
+            mean = self.mean + delta * n / tot
+            m2 = self.var * self.count + bm2 + delta * delta * self.count * n / tot
+            self.mean.copy_(mean)
+            self.var.copy_(m2 / tot)
+            self.count.copy_(tot)
+        self.derive()
+
+    @torch.no_grad()
+    def update(self, x):
+        """Merge the rows of ``x`` (and, data parallel, of every rank's ``x``, in rank order) into the statistics."""
+        part = self.batch_moments(x)
+        if _world() > 1:
+            parts = torch.empty(_world() * part.numel(), dtype=part.dtype, device=part.device)   # rank-major
+            dist.all_gather_into_tensor(parts, part)
+            part = parts
+        self.merge(part)
+
+    def state_dict(self):
+        return {"mean": self.mean.clone(), "var": self.var.clone(), "count": self.count.clone()}
+
+    @torch.no_grad()
+    def load_state(self, sd):
+        for k in ("mean", "var", "count"):
+            getattr(self, k).copy_(sd[k])
+        self.derive()
+
+
+def linear_tanh_small_k_norm(x, norm, weight, bias):
+    """``linear_tanh_small_k`` of the normalised rows, tanh(norm(x) Wᵀ + b), with the normalisation as the kernel's
+    load prologue (``ouz_linear_tanh_small_k_norm``; no autograd): bit for bit ``norm.normalize`` then
+    ``linear_tanh_small_k``, in one launch."""
+    x = x.contiguous()
+    w, b = weight.detach().contiguous(), bias.detach().contiguous()
+    y = torch.empty((x.shape[0], w.shape[0]), device=x.device)
+    L.check(L.lib.ouz_linear_tanh_small_k_norm(x.data_ptr(), norm.m.data_ptr(), norm.r.data_ptr(), norm.clip,
+                                               w.data_ptr(), b.data_ptr(), x.shape[0], w.shape[1], w.shape[0],
+                                               y.data_ptr(), L.stream_ptr(x.device)), "ouz_linear_tanh_small_k_norm")
     return y
 
 
@@ -303,15 +454,26 @@ def _tanh_fusable(layer, x, min_rows):
             and cols & (cols - 1) == 0)
 
 
-def run_mlp(seq, x, min_rows=8192, shadows=None):
+def run_mlp(seq, x, min_rows=8192, shadows=None, norm=None):
     """Forward through an nn.Sequential of Linear / activation modules using ``linear``; a Linear followed by a
     Tanh becomes one ``LinearTanh`` where its rows and width allow, and, without autograd (the rollout's policy and
     value calls), a first layer of K <= 16 inputs + its Tanh one ``linear_tanh_small_k`` pass at any row count.
-    ``shadows`` (a ``Bf16Shadows``: the learner's bf16 GEMM mode) sends the update's calls through ``run_mlp_bf16``."""
-    if bf16_ok(seq, x, min_rows, shadows):
-        return run_mlp_bf16(seq, x, shadows)
+    ``shadows`` (a ``Bf16Shadows``: the learner's bf16 GEMM mode) sends the update's calls through ``run_mlp_bf16``.
+    ``norm`` (a ``RunningNorm``: the learner's ``normalize_input``) normalises ``x`` first: without autograd as the
+    load prologue of that first layer (``linear_tanh_small_k_norm``: no launch of its own), otherwise as a pass of
+    its own (``norm.normalize``)."""
     mods = list(seq)
     i = 0
+    if norm is not None:
+        m = mods[0] if len(mods) > 1 and isinstance(mods[1], torch.nn.Tanh) else None
+        if (isinstance(m, torch.nn.Linear) and not torch.is_grad_enabled() and _fused_norm(x)
+                and smallk_ok(x, m.weight, m.bias)):
+            x = linear_tanh_small_k_norm(x, norm, m.weight, m.bias)
+            i = 2
+        else:
+            x = norm.normalize(x)
+    if i == 0 and bf16_ok(seq, x, min_rows, shadows):
+        return run_mlp_bf16(seq, x, shadows)
     while i < len(mods):
         m = mods[i]
         if isinstance(m, torch.nn.Linear) and i + 1 < len(mods) and isinstance(mods[i + 1], torch.nn.Tanh):

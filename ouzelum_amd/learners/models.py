@@ -54,22 +54,26 @@ class MLPActor(nn.Module):
         )
         self.actor_logstd = nn.Parameter(torch.zeros(1, n_act))
         self.gemm_shadows = None   # a fused.Bf16Shadows: the learner's bf16 GEMM mode (PPOLearner sets it)
+        # a fused.RunningNorm every input goes through first (PPOLearner's normalize_input attaches it, and takes
+        # it off around the update's calls, whose rows are normalised once beforehand)
+        self.obs_norm = None
 
     def forward(self, state, action=None, eps=None):
         head = self.actor_mean[-1]
         if action is None and _SAMPLE_FORM == "direct":
-            hidden = run_mlp(self.actor_mean[:-1], state)
+            hidden = run_mlp(self.actor_mean[:-1], state, norm=self.obs_norm)
             if policy_sample_ok(hidden, head):
                 e = torch.randn((hidden.shape[0], L_NUM_ACT), device=hidden.device) if eps is None else eps
                 return policy_sample(hidden, head, self.actor_logstd, e)
             return _policy_head(torch.nn.functional.linear(hidden, head.weight, head.bias), self.actor_logstd,
                                 action, self.rpo_alpha, eps)
-        mean = run_mlp(self.actor_mean, state, shadows=self.gemm_shadows)
+        mean = run_mlp(self.actor_mean, state, shadows=self.gemm_shadows, norm=self.obs_norm)
         return _policy_head(mean, self.actor_logstd, action, self.rpo_alpha, eps)
 
     def update_mean(self, state):
         """The mean the policy update scores its actions under (RPO's noise added), for ``fused.PolicyLoss``."""
-        return _rpo_mean(run_mlp(self.actor_mean, state, shadows=self.gemm_shadows), self.rpo_alpha)
+        return _rpo_mean(run_mlp(self.actor_mean, state, shadows=self.gemm_shadows, norm=self.obs_norm),
+                         self.rpo_alpha)
 
 
 class LSTMActor(nn.Module):
@@ -95,6 +99,7 @@ class LSTMActor(nn.Module):
         # (h, c) buffers of shape (1, B, H) that inference calls write their final carry into (GraphedPolicy)
         self.carry_inplace = None
         self.gemm_shadows = None   # a fused.Bf16Shadows: the learner's bf16 GEMM mode (PPOLearner sets it)
+        self.obs_norm = None       # a fused.RunningNorm every input goes through first (see MLPActor)
 
     def initial_state(self, num_envs, device):
         shape = (self.lstm.num_layers, num_envs, self.lstm.hidden_size)
@@ -106,7 +111,10 @@ class LSTMActor(nn.Module):
         # the bf16 GEMM mode (the update's calls only): bf16 trunk features into a bf16 input projection whose f32
         # result enters the sequence kernels; the recurrence and the mean head stay f32
         bf16 = bf16_ok(self.network, state, 8192, self.gemm_shadows)
-        feats = run_mlp_bf16(self.network, state, self.gemm_shadows) if bf16 else run_mlp(self.network, state)
+        if bf16 and self.obs_norm is not None:
+            state = self.obs_norm.normalize(state)
+        feats = (run_mlp_bf16(self.network, state, self.gemm_shadows) if bf16
+                 else run_mlp(self.network, state, norm=self.obs_norm))
         h, c = lstm_state
         B = h.shape[1]
         H = self.lstm.hidden_size
@@ -215,6 +223,7 @@ class Critic(nn.Module):
             layer_init(nn.Linear(256, 1), std=1.0),
         )
         self.gemm_shadows = None   # a fused.Bf16Shadows: the learner's bf16 GEMM mode (PPOLearner sets it)
+        self.obs_norm = None       # a fused.RunningNorm every input goes through first (see MLPActor)
 
     def forward(self, state):
-        return run_mlp(self.critic, state, shadows=self.gemm_shadows)
+        return run_mlp(self.critic, state, shadows=self.gemm_shadows, norm=self.obs_norm)

@@ -26,15 +26,22 @@ Differences, all MI355X-side:
 * ``gemm_dtype="bf16"`` (opt-in; DESIGN.md §9.1 "Precision contract"): the update's large trunk products take bf16
   operands with f32 accumulation, from bf16 shadows of the f32 master weights that the optimizer step keeps current.
   Everything without autograd (the rollout policy, the value pass before GAE, ``--play``) keeps the f32 weights.
+* ``normalize_input`` / ``normalize_value`` (opt-in): running normalisation of each network's
+  observations and of the value targets (``fused.RunningNorm``, f64 statistics on the device).  The calls without
+  autograd normalise inside the first layer's kernel; the update normalises its T·N rows once per stream.  The input
+  statistics merge a rollout AFTER its update, so the update scores the rollout under the statistics it was
+  collected under; the value statistics merge the returns before the targets are formed.
 """
+import contextlib
 import os
 
+import numpy as np
 import torch
 import torch.distributed as dist
 import torch.nn as nn
 
 from .. import _lib as L
-from .fused import Bf16Shadows, ClipAdam, PolicyLossEnt, ValueLoss, ValueLossClipped
+from .fused import Bf16Shadows, ClipAdam, PolicyLossEnt, RunningNorm, ValueLoss, ValueLossClipped
 from .gemm_tuning import enable_tuned_gemms
 from .models import Critic, LSTMActor, MLPActor
 
@@ -96,16 +103,19 @@ def gae(rewards, values, dones, next_value, next_done, gamma=0.99, lam=0.95):
 
 
 GEMM_DTYPES = ("f32", "bf16")
+OBS_CLIP = 5.0   # normalised observations are clamped to +-5; normalised values are not clamped
 
 
 class PPOLearner:
     def __init__(self, observation_space, action_space, num_envs, device, recurrent=True, rollout_steps=16,
                  lr=0.0026, num_minibatches=2, update_epochs=4, tuned_gemms=True, rpo_alpha=None, gemm_dtype="f32",
                  gamma=0.99, gae_lambda=0.95, clip_coef=0.2, norm_adv=True, ent_coef=0.0, vf_coef=2, clip_vloss=False,
-                 target_kl=None, max_grad_norm=1):
+                 target_kl=None, max_grad_norm=1, normalize_input=False, normalize_value=False):
         """The keywords after ``gemm_dtype`` are the reference update's knobs (agent.py:14-25) at its values; each
         becomes the attribute of its name (``gae_lambda``: ``gae_lamda``, the reference's spelling), which may also
-        be set after construction."""
+        be set after construction.  ``normalize_input`` / ``normalize_value`` (fixed at construction)
+        give each network a running normaliser of its observations (clip 5) and put the critic's output in the
+        normalised units of the returns."""
         if gemm_dtype not in GEMM_DTYPES:
             raise ValueError(f"gemm_dtype must be one of {GEMM_DTYPES}, not {gemm_dtype!r}")
         if gemm_dtype == "bf16" and torch.device(device).type != "cuda":
@@ -152,6 +162,19 @@ class PPOLearner:
         self.critic = Critic(observation_space).to(self.device)
         broadcast_params(self.actor)
         broadcast_params(self.critic)
+        # running normalisation (fused.RunningNorm): one normaliser per network over the stream it trains on (the
+        # actor's: the POMDP stream, or the observations for the single-stream learners; the critic's: the
+        # observations), read by every call of that network, and one over the returns.  Every rank starts from the
+        # same statistics and merges the same triples, so they need no broadcast.
+        self.normalize_input, self.normalize_value = bool(normalize_input), bool(normalize_value)
+        n_obs = int(np.prod(observation_space.shape))
+        self.actor_norm = self.critic_norm = self.value_norm = None
+        if self.normalize_input:
+            self.actor_norm = RunningNorm(n_obs, self.device, clip=OBS_CLIP)
+            self.critic_norm = RunningNorm(n_obs, self.device, clip=OBS_CLIP)
+            self.actor.obs_norm, self.critic.obs_norm = self.actor_norm, self.critic_norm
+        if self.normalize_value:
+            self.value_norm = RunningNorm(1, self.device)
         # the bf16 GEMM mode: bf16 shadows of both networks' GEMM weights, made after the broadcast
         self._shadows = None
         if gemm_dtype == "bf16":
@@ -206,9 +229,32 @@ class PPOLearner:
         return self._graphed(state, lstm_state, done, alias=alias)
 
     @torch.no_grad()
+    def _raw_values(self, v):
+        """The critic's outputs in the units of the returns: with ``normalize_value`` the critic works in normalised
+        units, denormalised here under the statistics in force."""
+        if self.value_norm is None:
+            return v
+        return self.value_norm.denormalize(v.reshape(-1, 1)).reshape(v.shape)
+
+    @torch.no_grad()
     def get_gae(self, next_obs, next_done, rewards, dones, values):
-        next_value = self.critic(next_obs).reshape(-1)
+        """``values``: in the units of the rewards (``_raw_values`` of the critic's outputs)."""
+        next_value = self._raw_values(self.critic(next_obs).reshape(-1))
         return gae(rewards, values, dones, next_value, next_done, self.gamma, self.gae_lamda)
+
+    @contextlib.contextmanager
+    def _inputs_prenormalized(self):
+        """The networks without their input normalisers: the update's minibatches are rows of copies that were
+        normalised once beforehand."""
+        nets = (self.actor, self.critic)
+        saved = [net.obs_norm for net in nets]
+        for net in nets:
+            net.obs_norm = None
+        try:
+            yield
+        finally:
+            for net, norm in zip(nets, saved):
+                net.obs_norm = norm
 
     # ------------------------------------------------------------------- update
     def _perm(self, n):
@@ -220,21 +266,39 @@ class PPOLearner:
         (RPO-LSTM trains on the POMDP-corrupted ones, agent.py:83); pass ``obs`` for plain PPO."""
         T, N = rewards.shape
         with torch.no_grad():
-            values = self.critic(obs.reshape(T * N, -1)).reshape(T, N)
+            values = self._raw_values(self.critic(obs.reshape(T * N, -1))).reshape(T, N)
         returns, advantages = self.get_gae(next_obs, next_done, rewards, dones, values)
-        b_obs = obs.reshape(T * N, -1)
-        b_pomdps = pomdps.reshape(T * N, -1)
-        b_actions = actions.reshape(T * N, -1)
-        b_logprobs = logprobs.reshape(-1)
-        b_dones = dones.reshape(-1)
-        b_advantages = advantages.reshape(-1)
-        b_returns = returns.reshape(-1)
+        raw_obs = b_obs = obs.reshape(T * N, -1)
+        raw_pomdps = b_pomdps = pomdps.reshape(T * N, -1)
+        b_returns, b_values = returns.reshape(-1), values.reshape(-1)
+        if self.normalize_input:
+            # normalised copies of the T·N rows, once per update per stream, under the statistics the rollout was
+            # collected under (they are merged after the last optimizer step, below)
+            b_obs, b_pomdps = self.critic_norm.normalize(raw_obs), self.actor_norm.normalize(raw_pomdps)
+        if self.value_norm is not None:
+            # GAE ran on raw rewards and raw values; the targets (and the clipped loss's old values) are in the
+            # units of the statistics that include this rollout's returns.  Advantages stay raw.
+            self.value_norm.update(b_returns.reshape(-1, 1))
+            b_returns = self.value_norm.normalize(b_returns.reshape(-1, 1)).reshape(-1)
+            if self.clip_vloss:
+                b_values = self.value_norm.normalize(b_values.reshape(-1, 1)).reshape(-1)
+        with self._inputs_prenormalized():
+            stats = self._update(T, N, b_obs, b_pomdps, actions.reshape(T * N, -1), logprobs.reshape(-1),
+                                 dones.reshape(-1), advantages.reshape(-1), b_returns, b_values, initial_lstm_state)
+        if self.normalize_input:
+            self.actor_norm.update(raw_pomdps)
+            self.critic_norm.update(raw_obs)
+        return stats
+
+    def _update(self, T, N, b_obs, b_pomdps, b_actions, b_logprobs, b_dones, b_advantages, b_returns, b_values,
+                initial_lstm_state):
+        """The epochs of minibatch steps on the flattened (T·N) rollout (``train``)."""
         flatinds = torch.arange(T * N, device=self.device).reshape(T, N)
         # the minibatch's four per-row scalars as ONE gather of their stacked rows (each result row contiguous)
         # instead of four (OUZ_STACKED_GATHER=0: one per tensor); exact either way
         scalars = [b_logprobs, b_dones, b_advantages, b_returns]
         if self.clip_vloss:   # the rollout's values (agent.py:107) as a fifth row of the same gather
-            scalars.append(values.reshape(-1))
+            scalars.append(b_values)
         stacked = (torch.stack([x.float() for x in scalars]) if self.device.type == "cuda"
                    and os.environ.get("OUZ_STACKED_GATHER", "1") != "0" else None)
         clipfracs = torch.zeros((), device=self.device)
@@ -342,15 +406,36 @@ class PPOLearner:
 
     # -------------------------------------------------------------- checkpoints
     def save(self, filename):
-        """Same four files as agent.py:127-131."""
+        """Same four files as agent.py:127-131; with ``normalize_input`` / ``normalize_value`` a fifth,
+        ``<filename>_normalizers``: the f64 statistics of each normaliser in use."""
         torch.save(self.critic.state_dict(), filename + "_critic")
         torch.save(self.critic_optimizer.state_dict(), filename + "_critic_optimizer")
         torch.save(self.actor.state_dict(), filename + "_actor")
         torch.save(self.actor_optimizer.state_dict(), filename + "_actor_optimizer")
+        norms = self._normalizers()
+        if norms:
+            torch.save({k: n.state_dict() for k, n in norms.items()}, filename + "_normalizers")
+
+    def _normalizers(self):
+        return {k: n for k, n in (("actor_input", self.actor_norm), ("critic_input", self.critic_norm),
+                                  ("value", self.value_norm)) if n is not None}
 
     def load(self, filename):
-        """agent.py:133-139; tensors only (weights_only)."""
+        """agent.py:133-139; tensors only (weights_only).  With a normalisation flag on, the fifth file is required
+        (a policy trained on normalised inputs is another function of the raw ones)."""
         m = self.device
+        norms = self._normalizers()
+        if norms:
+            path = filename + "_normalizers"
+            if not os.path.exists(path):
+                raise FileNotFoundError(f"{path}: this learner normalises ({', '.join(norms)}) and needs the "
+                                        "statistics the checkpoint was trained with")
+            saved = torch.load(path, map_location=m, weights_only=True)
+            missing = [k for k in norms if k not in saved]
+            if missing:
+                raise KeyError(f"{path} holds no statistics for {missing}")
+            for k, n in norms.items():
+                n.load_state(saved[k])
         self.critic.load_state_dict(torch.load(filename + "_critic", map_location=m, weights_only=True))
         self.critic_optimizer.load_state_dict(torch.load(filename + "_critic_optimizer", map_location=m,
                                                          weights_only=True))

@@ -33,6 +33,10 @@ The update's knobs are flags at the reference's values (``--lr``, ``--update_epo
 them.  ``--run_tag TAG`` appends ``_TAG`` to the run and checkpoint names, so a tuned run does not overwrite the
 reference-named one.  The new per-update values (``entropy``, ``v_clipfrac``, ``epochs_run``) go to the returned
 history only: the CSV columns and the event tags are the reference's.
+
+``--normalize_input`` / ``--normalize_value`` turn on the learner's running normalisation of observations and value
+targets (off by default).  Checkpoints then carry a fifth file, ``<name>_normalizers``, and ``--play``
+with the same flags loads its statistics and applies them without updating them.
 """
 import argparse
 import csv
@@ -96,6 +100,11 @@ def parse_args(argv=None):
     p.add_argument("--rpo_alpha", type=float, default=None, help="overrides the learner row's value in training; --play ignores it like the rest of the update's "
                         "flags, so a policy trained with another alpha plays with the row's value")
     p.add_argument("--run_tag", default=None, help="appended to the run and checkpoint names (default: the reference's names)")
+    # running normalisation; with --play: load the checkpoint's statistics and apply them unchanged
+    p.add_argument("--normalize_input", action="store_true",
+                   help="running mean / variance normalisation of each network's observations (clipped to +-5)")
+    p.add_argument("--normalize_value", action="store_true",
+                   help="the critic learns the returns normalised by their running mean / variance")
     args = p.parse_args(argv)
     if args.learner is not None:
         # given explicitly (their defaults say nothing): a second look at the same argv with no defaults
@@ -117,12 +126,20 @@ def variant_of(args):
 
 
 def learner_kwargs(args, v):
-    """PPOLearner's update keywords from the flags; ``--rpo_alpha`` overrides the row's value."""
-    return {"lr": args.lr, "update_epochs": args.update_epochs, "num_minibatches": args.num_minibatches,
-            "gamma": args.gamma, "gae_lambda": args.gae_lambda, "clip_coef": args.clip_coef, "vf_coef": args.vf_coef,
-            "max_grad_norm": args.max_grad_norm, "norm_adv": not args.no_norm_adv, "ent_coef": args.ent_coef,
-            "clip_vloss": args.clip_vloss, "target_kl": args.target_kl,
-            "rpo_alpha": v.rpo_alpha if args.rpo_alpha is None else args.rpo_alpha}
+    """PPOLearner's update keywords from the flags; ``--rpo_alpha`` overrides the row's value.  The normalisation
+    keywords are passed only when their flag is given (the constructor's default is off)."""
+    kw = {"lr": args.lr, "update_epochs": args.update_epochs, "num_minibatches": args.num_minibatches,
+          "gamma": args.gamma, "gae_lambda": args.gae_lambda, "clip_coef": args.clip_coef, "vf_coef": args.vf_coef,
+          "max_grad_norm": args.max_grad_norm, "norm_adv": not args.no_norm_adv, "ent_coef": args.ent_coef,
+          "clip_vloss": args.clip_vloss, "target_kl": args.target_kl,
+          "rpo_alpha": v.rpo_alpha if args.rpo_alpha is None else args.rpo_alpha}
+    kw.update(normalization_kwargs(args))
+    return kw
+
+
+def normalization_kwargs(args):
+    """``--normalize_input`` / ``--normalize_value`` as PPOLearner keywords (training and ``--play``)."""
+    return {k: True for k in ("normalize_input", "normalize_value") if getattr(args, k, False)}
 
 
 def run_names(args, v):
@@ -350,7 +367,8 @@ def play(args):
                 track_episodes=True)
     env = ExtractObsWrapper(base)
     agent = PPOLearner(base.observation_space, base.action_space, N, device, recurrent=v.recurrent,
-                       rollout_steps=args.rollout_steps, tuned_gemms=False, rpo_alpha=v.rpo_alpha)   # inference only
+                       rollout_steps=args.rollout_steps, tuned_gemms=False, rpo_alpha=v.rpo_alpha,   # inference only
+                       **normalization_kwargs(args))   # the checkpoint's statistics, never updated here
     if args.checkpoint:
         agent.load(args.checkpoint)
     pomdp_w = POMDPWrapper(args.POMDP, args.pomdp_prob, seed=args.seed + 1)
