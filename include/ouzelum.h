@@ -404,6 +404,16 @@ int ouz_gae(const float* rewards, const float* values, const float* dones, const
             const float* next_done, int32_t T, int32_t N, float gamma, float gamma_lam, float* advantages,
             float* returns, void* stream);
 
+/* ouz_gae with the critic's value kept at time-limit episode ends (rl_games' value_bootstrap).
+ * timeouts [T][N] and next_timeout [N] are the env's time_outs bytes, aligned with dones / next_done; any non-zero
+ * byte is "set".  Where the successor's done is a time-out, delta keeps gamma * V(successor) (values[t+1] is the value
+ * of the terminal observation: resets are lazy); the lambda chain is still cut by every done.  Row 0 of timeouts,
+ * like row 0 of dones, influences no output.  With every byte zero the outputs are ouz_gae's bits.  Everything else
+ * as in ouz_gae; a null timeouts / next_timeout is OUZ_ERR_INVALID. */
+int ouz_gae_bootstrap(const float* rewards, const float* values, const float* dones, const uint8_t* timeouts,
+                      const float* next_value, const float* next_done, const uint8_t* next_timeout, int32_t T,
+                      int32_t N, float gamma, float gamma_lam, float* advantages, float* returns, void* stream);
+
 /* POMDPWrapper.observation (utils/POMDP.py:23-43) applied by the learner to a
  * (rows, dim) f32 batch (RPO-LSTM/main.py:103): flicker zeroes the whole batch
  * with one coin per call, random_noise multiplies by U(1-prob, 1+prob) per

@@ -50,6 +50,35 @@ __global__ void __launch_bounds__(256) gae_kernel(const float* __restrict__ rew,
   }
 }
 
+// gae_kernel with the value bootstrap at time-limit episode ends: `nb` replaces `nnt` in delta only,
+// 1 where the successor is not done OR its done is a time-out (any non-zero byte), so the successor's value is kept
+// at a time-out; the lambda chain is still cut by every done.  The time-out rows are the env's bytes, read
+// coalesced (one byte per lane).  With every byte zero nb == nnt and the outputs are gae_kernel's bits.
+__global__ void __launch_bounds__(256) gae_bootstrap_kernel(
+    const float* __restrict__ rew, const float* __restrict__ val, const float* __restrict__ done,
+    const uint8_t* __restrict__ tmo, const float* __restrict__ next_val, const float* __restrict__ next_done,
+    const uint8_t* __restrict__ next_tmo, int T, int N, float gamma, float gamma_lam, float* __restrict__ adv,
+    float* __restrict__ ret) {
+#pragma clang fp contract(off)   // torch's f32 op order, one rounding per operation
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= N) return;
+  float last = 0.0f;
+  float nv = next_val[i];
+  float nnt = 1.0f - next_done[i];
+  float nb = next_tmo[i] ? 1.0f : nnt;
+  for (int t = T - 1; t >= 0; --t) {
+    const size_t k = (size_t)t * N + i;
+    const float v = val[k];
+    const float delta = (rew[k] + (gamma * nv) * nb) - v;
+    last = delta + (gamma_lam * nnt) * last;
+    adv[k] = last;
+    ret[k] = last + v;
+    nv = v;
+    nnt = 1.0f - done[k];
+    nb = tmo[k] ? 1.0f : nnt;
+  }
+}
+
 __global__ void __launch_bounds__(256) pomdp_obs_kernel(const float* __restrict__ in, float* __restrict__ out,
                                                         int rows, int dim, int zero, int noise, float lo, float hi,
                                                         uint64_t seed, uint32_t row0, uint32_t call) {
@@ -1323,6 +1352,18 @@ int ouz_gae(const float* rewards, const float* values, const float* dones, const
   hipLaunchKernelGGL(gae_kernel, dim3(grid(N, 256)), dim3(256), 0, (hipStream_t)stream, rewards, values, dones,
                      next_value, next_done, T, N, gamma, gamma_lam, advantages, returns);
   return launch_status("gae_kernel");
+}
+
+int ouz_gae_bootstrap(const float* rewards, const float* values, const float* dones, const uint8_t* timeouts,
+                      const float* next_value, const float* next_done, const uint8_t* next_timeout, int32_t T,
+                      int32_t N, float gamma, float gamma_lam, float* advantages, float* returns, void* stream) {
+  if (T <= 0 || N <= 0) return set_error(OUZ_ERR_INVALID, "ouz_gae_bootstrap: T and N must be > 0");
+  if (!rewards || !values || !dones || !next_value || !next_done || !advantages || !returns)
+    return set_error(OUZ_ERR_INVALID, "ouz_gae_bootstrap: null buffer");
+  if (!timeouts || !next_timeout) return set_error(OUZ_ERR_INVALID, "ouz_gae_bootstrap: null time-out buffer");
+  hipLaunchKernelGGL(gae_bootstrap_kernel, dim3(grid(N, 256)), dim3(256), 0, (hipStream_t)stream, rewards, values,
+                     dones, timeouts, next_value, next_done, next_timeout, T, N, gamma, gamma_lam, advantages, returns);
+  return launch_status("gae_bootstrap_kernel");
 }
 
 int ouz_pomdp_obs(const float* in, float* out, int32_t rows, int32_t dim, int32_t mode, float prob, uint64_t seed,

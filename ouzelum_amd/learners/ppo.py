@@ -31,6 +31,9 @@ Differences, all MI355X-side:
   autograd normalise inside the first layer's kernel; the update normalises its T·N rows once per stream.  The input
   statistics merge a rollout AFTER its update, so the update scores the rollout under the statistics it was
   collected under; the value statistics merge the returns before the targets are formed.
+* ``value_bootstrap`` (opt-in): GAE keeps ``gamma * V(terminal observation)`` where an episode ended by
+  its time limit (``ouz_gae_bootstrap``: the same one launch, reading the env's ``time_outs`` bytes).  The terminal
+  observation's value is already among the update's values, because the env resets lazily.
 """
 import contextlib
 import os
@@ -88,15 +91,34 @@ def allreduce_grads(module):
         off += n
 
 
-def gae(rewards, values, dones, next_value, next_done, gamma=0.99, lam=0.95):
-    """(returns, advantages), each (T, N) f32, from the HIP kernel (RPO-LSTM/agent.py:40-55)."""
+_TIMEOUT_DTYPES = (torch.bool, torch.uint8)
+
+
+def gae(rewards, values, dones, next_value, next_done, gamma=0.99, lam=0.95, timeouts=None, next_timeout=None):
+    """(returns, advantages), each (T, N) f32, from the HIP kernel (RPO-LSTM/agent.py:40-55).  With ``timeouts``
+    (T, N) and ``next_timeout`` (N), the env's ``time_outs`` bytes (torch.bool or torch.uint8, contiguous) aligned
+    with ``dones`` / ``next_done``, the successor's value is kept where its done is a time-out
+    (``ouz_gae_bootstrap``); both or neither."""
+    if (timeouts is None) != (next_timeout is None):
+        raise ValueError("timeouts and next_timeout go together: both or neither")
     T, N = rewards.shape
     ts = [t.contiguous().float() for t in (rewards, values, dones, next_value.reshape(N), next_done.reshape(N))]
     for t, name in zip(ts, ("rewards", "values", "dones", "next_value", "next_done")):
         L.require_hip_tensor(t, name)
+    if timeouts is not None:
+        for t, name, shape in ((timeouts, "timeouts", (T, N)), (next_timeout, "next_timeout", (N,))):
+            if t.dtype not in _TIMEOUT_DTYPES or tuple(t.shape) != shape or not t.is_contiguous():
+                raise ValueError(f"{name} must be a contiguous {shape} torch.bool or torch.uint8 tensor (the env's "
+                                 f"bytes), not {tuple(t.shape)} {t.dtype}")
+            L.require_hip_tensor(t, name)
     adv = torch.empty_like(ts[0])
     ret = torch.empty_like(ts[0])
     # the reference multiplies by the Python product gamma * lambda (a double), rounded once to f32
+    if timeouts is not None:
+        L.check(L.lib.ouz_gae_bootstrap(L.ptr(ts[0]), L.ptr(ts[1]), L.ptr(ts[2]), L.ptr(timeouts), L.ptr(ts[3]),
+                                        L.ptr(ts[4]), L.ptr(next_timeout), T, N, gamma, float(gamma * lam),
+                                        L.ptr(adv), L.ptr(ret), L.stream_ptr(adv.device)), "ouz_gae_bootstrap")
+        return ret, adv
     L.check(L.lib.ouz_gae(*(L.ptr(t) for t in ts), T, N, gamma, float(gamma * lam), L.ptr(adv), L.ptr(ret),
                           L.stream_ptr(adv.device)), "ouz_gae")
     return ret, adv
@@ -110,12 +132,17 @@ class PPOLearner:
     def __init__(self, observation_space, action_space, num_envs, device, recurrent=True, rollout_steps=16,
                  lr=0.0026, num_minibatches=2, update_epochs=4, tuned_gemms=True, rpo_alpha=None, gemm_dtype="f32",
                  gamma=0.99, gae_lambda=0.95, clip_coef=0.2, norm_adv=True, ent_coef=0.0, vf_coef=2, clip_vloss=False,
-                 target_kl=None, max_grad_norm=1, normalize_input=False, normalize_value=False):
+                 target_kl=None, max_grad_norm=1, normalize_input=False, normalize_value=False,
+                 value_bootstrap=False):
         """The keywords after ``gemm_dtype`` are the reference update's knobs (agent.py:14-25) at its values; each
         becomes the attribute of its name (``gae_lambda``: ``gae_lamda``, the reference's spelling), which may also
         be set after construction.  ``normalize_input`` / ``normalize_value`` (fixed at construction)
         give each network a running normaliser of its observations (clip 5) and put the critic's output in the
-        normalised units of the returns."""
+        normalised units of the returns.  ``value_bootstrap`` (off by default): GAE keeps the
+        critic's value of the terminal observation where an episode ended by its time limit; ``train`` / ``get_gae``
+        then need the rollout's ``timeouts`` / ``next_timeout``."""
+        if not isinstance(value_bootstrap, (bool, np.bool_)):
+            raise ValueError(f"value_bootstrap must be a bool, not {value_bootstrap!r}")
         if gemm_dtype not in GEMM_DTYPES:
             raise ValueError(f"gemm_dtype must be one of {GEMM_DTYPES}, not {gemm_dtype!r}")
         if gemm_dtype == "bf16" and torch.device(device).type != "cuda":
@@ -129,6 +156,7 @@ class PPOLearner:
             if not 0 <= val <= 1:
                 raise ValueError(f"{name} must lie in [0, 1], not {val!r}")
         self.gemm_dtype = gemm_dtype
+        self.value_bootstrap = bool(value_bootstrap)
         self.obs_dim = observation_space
         self.act_dim = action_space
         self.num_envs = num_envs
@@ -237,10 +265,25 @@ class PPOLearner:
         return self.value_norm.denormalize(v.reshape(-1, 1)).reshape(v.shape)
 
     @torch.no_grad()
-    def get_gae(self, next_obs, next_done, rewards, dones, values):
-        """``values``: in the units of the rewards (``_raw_values`` of the critic's outputs)."""
+    def get_gae(self, next_obs, next_done, rewards, dones, values, *, timeouts=None, next_timeout=None):
+        """``values``: in the units of the rewards (``_raw_values`` of the critic's outputs).  With
+        ``value_bootstrap`` the time-out flags aligned with ``dones`` / ``next_done`` are required; without it they
+        are ignored."""
+        if self.value_bootstrap:
+            self._require_timeouts(timeouts, next_timeout)
         next_value = self._raw_values(self.critic(next_obs).reshape(-1))
-        return gae(rewards, values, dones, next_value, next_done, self.gamma, self.gae_lamda)
+        if not self.value_bootstrap:
+            return gae(rewards, values, dones, next_value, next_done, self.gamma, self.gae_lamda)
+        # raw rewards and raw values here too (``_raw_values``): the bootstrapped tail gamma * V(terminal obs) is in
+        # the units of the rewards, so ``normalize_value`` and ``clip_vloss`` see returns of the kind they saw before
+        return gae(rewards, values, dones, next_value, next_done, self.gamma, self.gae_lamda,
+                   timeouts=timeouts, next_timeout=next_timeout)
+
+    @staticmethod
+    def _require_timeouts(timeouts, next_timeout):
+        if timeouts is None or next_timeout is None:
+            raise ValueError("value_bootstrap=True needs the rollout's time-out flags: pass timeouts=(T, N) and "
+                             "next_timeout=(N,), the env's time_outs aligned with dones and next_done")
 
     @contextlib.contextmanager
     def _inputs_prenormalized(self):
@@ -261,13 +304,19 @@ class PPOLearner:
         """A uniform random permutation from device RNG (no host round trip)."""
         return torch.argsort(torch.rand(n, device=self.device))
 
-    def train(self, obs, pomdps, actions, next_obs, next_done, initial_lstm_state, logprobs, rewards, dones):
+    def train(self, obs, pomdps, actions, next_obs, next_done, initial_lstm_state, logprobs, rewards, dones, *,
+              timeouts=None, next_timeout=None):
         """One PPO update on a (T, N) rollout.  ``pomdps`` are the observations the actor trains on
-        (RPO-LSTM trains on the POMDP-corrupted ones, agent.py:83); pass ``obs`` for plain PPO."""
+        (RPO-LSTM trains on the POMDP-corrupted ones, agent.py:83); pass ``obs`` for plain PPO.  ``timeouts`` /
+        ``next_timeout``: the env's time-out flags aligned with ``dones`` / ``next_done``, required with
+        ``value_bootstrap`` and ignored without it."""
         T, N = rewards.shape
+        if self.value_bootstrap:
+            self._require_timeouts(timeouts, next_timeout)
         with torch.no_grad():
             values = self._raw_values(self.critic(obs.reshape(T * N, -1))).reshape(T, N)
-        returns, advantages = self.get_gae(next_obs, next_done, rewards, dones, values)
+        returns, advantages = self.get_gae(next_obs, next_done, rewards, dones, values, timeouts=timeouts,
+                                           next_timeout=next_timeout)
         raw_obs = b_obs = obs.reshape(T * N, -1)
         raw_pomdps = b_pomdps = pomdps.reshape(T * N, -1)
         b_returns, b_values = returns.reshape(-1), values.reshape(-1)
@@ -288,6 +337,11 @@ class PPOLearner:
         if self.normalize_input:
             self.actor_norm.update(raw_pomdps)
             self.critic_norm.update(raw_obs)
+        if self.value_bootstrap:
+            # the share of the T·N transitions whose successor was a time-out (rows 1.. and next_timeout; row 0
+            # belongs to the rollout before; any non-zero byte counts): one reduction, read by whoever reads the stats
+            flags = torch.cat([timeouts[1:].reshape(-1), next_timeout.reshape(-1)])
+            stats["timeout_frac"] = torch.count_nonzero(flags) / float(T * N)
         return stats
 
     def _update(self, T, N, b_obs, b_pomdps, b_actions, b_logprobs, b_dones, b_advantages, b_returns, b_values,

@@ -7,8 +7,8 @@ Runs ``python -m ouzelum_amd.learners.train --learner L --POMDP P --pomdp_prob p
 script's order (learner by learner; flicker, random_noise, flickering_and_random_noise), one after another, each a
 fresh child process, and stops at the first run that exits non-zero.  ``--dry_run`` prints the command lines and
 starts nothing.  Arguments this module does not know (``--env``, ``--num_envs``, ``--logdir``, ``--episode_log``,
-``--gemm_dtype``, the update's flags such as ``--ent_coef 0.01 --clip_vloss --anneal_lr --run_tag tuned`` ...) are
-handed to every run.
+``--gemm_dtype``, the update's flags such as ``--ent_coef 0.01 --clip_vloss --anneal_lr --run_tag tuned``,
+``--value_bootstrap``, ``--max_episode_length N`` ...) are handed to every run, and only when given.
 """
 import argparse
 import shlex

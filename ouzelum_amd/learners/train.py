@@ -37,6 +37,11 @@ history only: the CSV columns and the event tags are the reference's.
 ``--normalize_input`` / ``--normalize_value`` turn on the learner's running normalisation of observations and value
 targets (off by default).  Checkpoints then carry a fifth file, ``<name>_normalizers``, and ``--play``
 with the same flags loads its statistics and applies them without updating them.
+
+``--value_bootstrap`` (off by default) keeps the critic's value at episode ends caused by the time
+limit: the rollout then stores the env's ``time_outs`` beside the dones and GAE runs as ``ouz_gae_bootstrap``; the
+returned history carries ``timeout_frac``.  ``--max_episode_length N`` is the task YAML's ``maxEpisodeLength``.
+``--play`` ignores ``--value_bootstrap``.
 """
 import argparse
 import csv
@@ -105,6 +110,11 @@ def parse_args(argv=None):
                    help="running mean / variance normalisation of each network's observations (clipped to +-5)")
     p.add_argument("--normalize_value", action="store_true",
                    help="the critic learns the returns normalised by their running mean / variance")
+    # the critic's value kept at time-limit episode ends; --play ignores it like the update's knobs
+    p.add_argument("--value_bootstrap", action="store_true",
+                   help="GAE keeps gamma * V(terminal observation) where an episode ended by its time limit")
+    p.add_argument("--max_episode_length", type=int, default=None,
+                   help="the task YAML's maxEpisodeLength (default: the task's own)")
     args = p.parse_args(argv)
     if args.learner is not None:
         # given explicitly (their defaults say nothing): a second look at the same argv with no defaults
@@ -134,7 +144,15 @@ def learner_kwargs(args, v):
           "clip_vloss": args.clip_vloss, "target_kl": args.target_kl,
           "rpo_alpha": v.rpo_alpha if args.rpo_alpha is None else args.rpo_alpha}
     kw.update(normalization_kwargs(args))
+    if getattr(args, "value_bootstrap", False):
+        kw["value_bootstrap"] = True
     return kw
+
+
+def env_kwargs(args):
+    """``make``'s keywords from the flags: ``--max_episode_length`` only when given (the task's own otherwise)."""
+    n = getattr(args, "max_episode_length", None)
+    return {} if n is None else {"max_episode_length": int(n)}
 
 
 def normalization_kwargs(args):
@@ -212,6 +230,14 @@ class Rollout:
         if self.single:
             self.next_obs = self.pomdp        # a tensor of its own: the env overwrites its observation buffer in place
         self.next_done = torch.zeros(N, device=device)
+        # the env's time-out flags beside the dones, only for a learner with value_bootstrap, in
+        # the env's byte dtype: timeouts[k] came with obs[k], as dones[k] did.  next_timeout is a tensor of the
+        # rollout's own: the env overwrites its time_outs buffer in place on the next step.
+        self.bootstrap = bool(getattr(agent, "value_bootstrap", False))
+        self.timeouts = self.next_timeout = None
+        if self.bootstrap:
+            self.timeouts = torch.zeros((T, N), dtype=torch.bool, device=device)
+            self.next_timeout = torch.zeros(N, dtype=torch.bool, device=device)
         self.lstm_state = agent.initial_state()
         self.init_state = None
 
@@ -226,12 +252,20 @@ class Rollout:
         self.init_state = (lstm_state[0].clone(), lstm_state[1].clone()) if lstm_state is not None else None
         if per_episode:
             envs.begin_rollout()
+        # with value_bootstrap: the time-out flags that came with next_obs go into the same store call as the dones (the
+        # env's own buffer after the first step, copied before the next step overwrites it); without it the call is
+        # as it was
+        timeouts, next_to = self.timeouts, self.next_timeout
+        tmo_dst = tmo_src = ()
         for step in range(self.T):
+            if timeouts is not None:
+                tmo_dst, tmo_src = (timeouts[step],), (next_to,)
             if single:
-                store((obs[step], dones[step]), (next_obs, next_done))
+                store((obs[step], dones[step], *tmo_dst), (next_obs, next_done, *tmo_src))
                 act_in = next_obs
             else:
-                store((pomdps[step], obs[step], dones[step]), (pomdp, next_obs, next_done))  # one multi-tensor copy
+                store((pomdps[step], obs[step], dones[step], *tmo_dst),
+                      (pomdp, next_obs, next_done, *tmo_src))                                # one multi-tensor copy
                 act_in = pomdp if acts_on_pomdp else next_obs
             if seen is not None:
                 seen["acted_on"][step].copy_(act_in)
@@ -246,14 +280,19 @@ class Rollout:
                 next_obs = pomdp_w.observation(next_obs)     # PPO/main.py:96
             else:
                 pomdp = pomdp_w.observation(next_obs)        # RPO-LSTM/main.py:103
+            if timeouts is not None:
+                next_to = info["time_outs"]
             if seen is not None:
                 store((seen["dones"][step], seen["r"][step], seen["l"][step]), (next_done, info["r"], info["l"]))
+        if timeouts is not None:
+            self.next_timeout.copy_(next_to)
         self.next_obs, self.pomdp, self.next_done, self.lstm_state = next_obs, pomdp, next_done, lstm_state
 
     def update(self):
         """One PPO update on the rollout just collected; the actor trains on the POMDP stream."""
+        kw = {"timeouts": self.timeouts, "next_timeout": self.next_timeout} if self.bootstrap else {}
         return self.agent.train(self.obs, self.obs if self.single else self.pomdps, self.actions, self.next_obs,
-                                self.next_done, self.init_state, self.logprobs, self.rewards, self.dones)
+                                self.next_done, self.init_state, self.logprobs, self.rewards, self.dones, **kw)
 
 
 def train(args, on_rollout=None):
@@ -272,7 +311,8 @@ def train(args, on_rollout=None):
     off, total = shard(N, rank, world)
 
     base = make(seed=args.seed, task=args.env, num_envs=N, sim_device=str(device), rl_device=str(device),
-                graphics_device_id=-1, headless=True, env_id_offset=off, num_envs_total=total, track_episodes=True)
+                graphics_device_id=-1, headless=True, env_id_offset=off, num_envs_total=total, track_episodes=True,
+                **env_kwargs(args))
     envs = EpisodeRecorder(ExtractObsWrapper(base), device, env_id0=off, capacity=3 * N)
     pomdp_w = POMDPWrapper(args.POMDP, args.pomdp_prob, seed=args.seed + 1, row_offset=off)
     agent = PPOLearner(base.observation_space, base.action_space, N, device, recurrent=v.recurrent,
@@ -364,7 +404,7 @@ def play(args):
     device = torch.device("cuda", 0)
     N = args.num_envs
     base = make(seed=args.seed, task=args.env, num_envs=N, sim_device=str(device), rl_device=str(device),
-                track_episodes=True)
+                track_episodes=True, **env_kwargs(args))
     env = ExtractObsWrapper(base)
     agent = PPOLearner(base.observation_space, base.action_space, N, device, recurrent=v.recurrent,
                        rollout_steps=args.rollout_steps, tuned_gemms=False, rpo_alpha=v.rpo_alpha,   # inference only

@@ -40,6 +40,7 @@ ap.add_argument("--ent_coef", type=float, default=0.0)
 ap.add_argument("--clip_vloss", action="store_true")
 ap.add_argument("--update_epochs", type=int, default=4)
 ap.add_argument("--num_minibatches", type=int, default=2)
+ap.add_argument("--value_bootstrap", action="store_true")
 a = ap.parse_args()
 v = VARIANTS[a.learner] if a.learner else legacy_variant(a.algo, "clean")
 per_episode = a.learner is not None and a.episode_log == "per_episode"
@@ -52,9 +53,11 @@ if a.learner:
     env = EpisodeRecorder(env, dev, capacity=3 * N)
 agent = PPOLearner(base.observation_space, base.action_space, N, dev, recurrent=v.recurrent, rpo_alpha=v.rpo_alpha,
                    gemm_dtype=a.gemm_dtype, ent_coef=a.ent_coef, clip_vloss=a.clip_vloss,
-                   update_epochs=a.update_epochs, num_minibatches=a.num_minibatches)
+                   update_epochs=a.update_epochs, num_minibatches=a.num_minibatches,
+                   **({"value_bootstrap": True} if a.value_bootstrap else {}))
 options = {k: getattr(a, k) for k, d in (("ent_coef", 0.0), ("clip_vloss", False), ("update_epochs", 4),
-                                         ("num_minibatches", 2)) if getattr(a, k) != d}   # the ones given
+                                         ("num_minibatches", 2), ("value_bootstrap", False))
+           if getattr(a, k) != d}   # the ones given
 ro = Rollout(env, POMDPWrapper("flicker", 0.1, seed=1), agent, v, T)
 t_roll = t_upd = 0.0
 n_records = 0
