@@ -78,7 +78,9 @@ extern "C" {
                                9: the PPO update's options on the loss kernels (ouz_ppo_policy_loss_ent: entropy
                                   bonus; ouz_ppo_value_loss_clipped: clipped value loss); entry points added since
                                   with no struct or signature changed: the running normalisation (ouz_moments_batch,
-                                  ouz_moments_merge, ouz_normalize_rows, ouz_linear_tanh_small_k_norm) */
+                                  ouz_moments_merge, ouz_normalize_rows, ouz_linear_tanh_small_k_norm), the value
+                                  bootstrap (ouz_gae_bootstrap), the bounded atan2 beside the library's
+                                  (ouz_atan2_pair) */
 
 /* error codes */
 #define OUZ_OK 0
@@ -374,6 +376,10 @@ int ouz_set_step(ouz_env* env, int64_t step);
 /* component entry points (same device functions as the fused step) */
 int ouz_lee_control(int32_t mode, const float* state, const float* cmd, float* thrust, float* torque, int32_t n,
                     void* stream);
+/* The yaw of the step's zero-yaw-command position controller, atan2_bounded_f (quad_math.h: atan2f for finite
+ * arguments of magnitude <= 2^96), and the library atan2f of the same n pairs (y, x), side by side: the two are
+ * equal bit for bit under that precondition (tests/test_gpu_oneblock_rollout.py). */
+int ouz_atan2_pair(const float* y, const float* x, float* bounded, float* library, int32_t n, void* stream);
 int ouz_ekf_update(const float* q_wxyz, const float* P10, const float* gyr, const float* ang_wxyz, float dt,
                    float* q_out, float* P10_out, int32_t n, void* stream);
 int ouz_pv_predict(float* x9, float* P45, const float* acc, const float* q_wxyz, float dt, int32_t n,

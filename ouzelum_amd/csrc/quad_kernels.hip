@@ -1164,6 +1164,14 @@ __global__ void __launch_bounds__(64) lee_kernel(int mode, const float* s, const
   torque[i * 3 + 0] = tau.x; torque[i * 3 + 1] = tau.y; torque[i * 3 + 2] = tau.z;
 }
 
+// atan2_bounded_f (the zero-yaw controller's yaw) beside the library atan2f on the same pairs, for the bitwise test
+__global__ void __launch_bounds__(64) atan2_pair_kernel(const float* y, const float* x, float* bounded, float* library, int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  bounded[i] = atan2_bounded_f(y[i], x[i]);
+  library[i] = atan2f(y[i], x[i]);
+}
+
 __global__ void __launch_bounds__(64) ekf_kernel(const float* q, const float* P, const float* gyr, const float* ang, float dt, float* qo,
                            float* Po, int n) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -2073,6 +2081,14 @@ int ouz_lee_control(int32_t mode, const float* state, const float* cmd, float* t
   if (!state || !cmd || !thrust || !torque) return fail(OUZ_ERR_INVALID, "ouz_lee_control: null pointer");
   hipLaunchKernelGGL(lee_kernel, dim3(grid_for(n, 64)), dim3(64), 0, (hipStream_t)stream, mode, state, cmd, thrust, torque, n);
   OUZ_LAUNCH_CHECK("lee_kernel");
+  return OUZ_OK;
+}
+
+int ouz_atan2_pair(const float* y, const float* x, float* bounded, float* library, int32_t n, void* stream) {
+  OUZ_CHECK_N("ouz_atan2_pair");
+  if (!y || !x || !bounded || !library) return fail(OUZ_ERR_INVALID, "ouz_atan2_pair: null pointer");
+  hipLaunchKernelGGL(atan2_pair_kernel, dim3(grid_for(n, 64)), dim3(64), 0, (hipStream_t)stream, y, x, bounded, library, n);
+  OUZ_LAUNCH_CHECK("atan2_pair_kernel");
   return OUZ_OK;
 }
 

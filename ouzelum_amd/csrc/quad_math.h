@@ -219,6 +219,37 @@ OUZ_HD float remainder_small_f(float a, float b) {
   return m;
 }
 
+// atan2f under the precondition that x and y are finite with |x|, |y| <= 2^96 (the zero-yaw controller's arguments
+// are R10 and R00 of a normalised quaternion: magnitude at most 1 plus rounding).  On the device: the library
+// routine's own operations in its order (the quotient min * rcp(max), its eight-coefficient series in the squared
+// quotient, the octant folds, the y == 0 case, the sign of y) without its 2^96 range scaling, its both-infinite
+// case and its unordered case, which the precondition rules out: bit for bit atan2f there, one basic block.
+// Outside the precondition (infinities, NaN, larger magnitudes) the value is unspecified.  The host keeps atan2f.
+OUZ_HD float atan2_bounded_f(float y, float x) {
+#if defined(OUZ_HOST) || !defined(__HIP_DEVICE_COMPILE__)
+  return atan2f(y, x);
+#else
+  const float ax = fabsf(x), ay = fabsf(y);
+  const float mx = fmaxf(ax, ay), mn = fminf(ax, ay);
+  const float v = mn * __builtin_amdgcn_rcpf(mx);
+  const float t = v * v;
+  float s = fmaf(t, __uint_as_float(0x3b2d2a58u), __uint_as_float(0xbc7a590cu));
+  s = fmaf(t, s, __uint_as_float(0x3d29fb3fu));
+  s = fmaf(t, s, __uint_as_float(0xbd97d4d7u));
+  s = fmaf(t, s, __uint_as_float(0x3dd931b2u));
+  s = fmaf(t, s, __uint_as_float(0xbe1160e6u));
+  s = fmaf(t, s, __uint_as_float(0x3e4cb8bfu));
+  s = fmaf(t, s, __uint_as_float(0xbeaaaa62u));
+  const float ts = t * s;
+  float a = fmaf(v, ts, v);
+  a = ay > ax ? __uint_as_float(0x3fc90fdbu) - a : a;                                    // pi/2 - a
+  a = x < 0.0f ? __uint_as_float(0x40490fdbu) - a : a;                                   // pi - a
+  const float a0 = (int)__float_as_uint(x) < 0 ? __uint_as_float(0x40490fdbu) : 0.0f;    // y == 0: pi or 0 by x's sign bit
+  a = y == 0.0f ? a0 : a;
+  return __builtin_copysignf(a, y);
+#endif
+}
+
 // Shared attitude loop (position_control.py:66-108): returns torque.
 OUZ_HD V3 lee_attitude_loop(const M3& R, const M3& Rd, V3 omega, const EulerSC& e, float yaw_rate,
                             const LeeGains& g) {
@@ -257,7 +288,7 @@ OUZ_HD void lee_position_R(const M3& R, V3 p, V3 v, V3 w, V3 cmd_p, float cmd_ya
   b2 = (1.0f / norm(b2)) * b2;
   V3 b1 = cross(b2, b3);
   M3 Rd{{b1.x, b2.x, b3.x, b1.y, b2.y, b3.y, b1.z, b2.z, b3.z}};
-  const float ya = cmd_yaw - atan2f(R.m[3], R.m[0]);
+  const float ya = cmd_yaw - (kZeroYaw ? atan2_bounded_f(R.m[3], R.m[0]) : atan2f(R.m[3], R.m[0]));
   float yr = kZeroYaw ? remainder_small_f(ya, kTwoPiF) : remainder_f(ya, kTwoPiF);
   if (yr > kPiF) yr -= kTwoPiF;
   torque = lee_attitude_loop(R, Rd, w, e, yr, g);
@@ -855,7 +886,10 @@ OUZ_HD void integrate(V3& p, Q4& q, V3& v, V3& w, V3 f_b, V3 tau_b, float inv_m,
 // rollout hands it to its next step as R0).
 // SMALL: the launch guarantees 0.5 h wmax < 0.04 with margin (plain_config, quad_env.h): |w_b| <= wmax after the clamp
 // (or 0 on the deck), so every sub-step takes the series side of the angle test and that side is the only code.
-template <int NSUB, bool SMALL = false>
+// RARE_CLAMP: the caller's lanes are seldom above the body-rate clamp (the plain LeeLanded rollout: a controlled
+// hover); the clamp is then laid out of line and a sub-step without it falls through.  Not for the RL tasks, whose
+// random-action lanes sit at the clamp in most steps (QuadFault 8192 envs: -4.7 % env-steps/s with the hint).
+template <int NSUB, bool SMALL = false, bool RARE_CLAMP = false>
 OUZ_HD void integrate_thrust_body(V3& p, Q4& q, V3& v, V3& w, const M3& R0, float fz, V3 tau_b, float inv_m, V3 I,
                                   V3 inv_I, float h, float wmax, DeckContact deck, V3 g, int nsub = NSUB,
                                   M3* R_out = nullptr) {
@@ -873,7 +907,8 @@ OUZ_HD void integrate_thrust_body(V3& p, Q4& q, V3& v, V3& w, const M3& R0, floa
     const V3 c = cross(wb, mul(I, wb));
     wb = wb + h * mul(inv_I, tau_b - c);
     float n2 = dot(wb, wb);
-    if (n2 > wmax * wmax) { wb = (wmax / sqrtf(n2)) * wb; n2 = wmax * wmax; }
+    const bool over = n2 > wmax * wmax;
+    if (RARE_CLAMP ? __builtin_expect(over, 0) : over) { wb = (wmax / sqrtf(n2)) * wb; n2 = wmax * wmax; }
     p = p + h * v;
     if (deck.on) {
       const float dx = p.x - deck.px, dy = p.y - deck.py;
