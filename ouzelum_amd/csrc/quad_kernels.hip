@@ -100,10 +100,35 @@ __device__ __forceinline__ void emit_env(const OutPtrs& o, int e, bool valid, co
   }
 }
 
+// WT (out_wave, the plain LeeLanded rollout's storage rows): the row leaves as write-through (sc1) stores, so it is
+// not dirty in the XCD's L2 when the launch ends and the end-of-kernel writeback has that much less to flush
+// (K x n x 65 bytes otherwise: 8.5 MB at 4096 envs and 32 steps).  The 52-byte obs row as three 16-byte buffer stores
+// + one dword through a descriptor of the step's n rows (a lane past n is `valid`-masked; the descriptor's range check
+// is a second guard), reward and flags as relaxed agent-scope atomic stores (global_store ... sc1).  The bytes are
+// the plain form's.  Latency-regime launches only (the output wave's), every flag written (rollout storage).
+template <bool WT = false>
 __device__ __forceinline__ void emit(const OutPtrs& o, float* wave_lds, int i, int n, bool valid, const float* ob,
                                      float rew, bool rs, bool to, bool direct, bool keep_flags = false) {
   const uint32_t lane = (uint32_t)i & 63u;
   const uint32_t first = wave_tile(i) * 64u;   // wave-uniform: output bases live in SGPRs
+  if constexpr (WT) {
+    if (valid) {
+      typedef uint32_t u4v __attribute__((ext_vector_type(4)));
+      constexpr int kSc1 = 16;   // the buffer stores' aux bit of sc1
+      const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(o.obs, 0, n * (int)(OUZ_NUM_OBS * sizeof(float)), 0x00020000);
+      const int off = i * (int)(OUZ_NUM_OBS * sizeof(float));
+#pragma unroll
+      for (int r = 0; r < 3; ++r)
+        __builtin_amdgcn_raw_buffer_store_b128(u4v{__float_as_uint(ob[4 * r]), __float_as_uint(ob[4 * r + 1]),
+                                                   __float_as_uint(ob[4 * r + 2]), __float_as_uint(ob[4 * r + 3])},
+                                               rsrc, off + 16 * r, 0, kSc1);
+      __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(ob[12]), rsrc, off + 48, 0, kSc1);
+      __hip_atomic_store(&(o.rew + first)[lane], rew, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_store(&(o.reset + first)[lane], (int64_t)(rs ? 1 : 0), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_store(&(o.timeouts + first)[lane], (uint8_t)(to ? 1 : 0), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    return;
+  }
   if (n <= kLatencyRegimeEnvs && !direct) {
     // Latency regime (a few waves per CU, the step is one dependent chain): each lane stores its own
     // 52-byte row as three 16-byte stores + one dword (rows are 4-byte aligned; gfx950 global stores
@@ -397,7 +422,7 @@ __device__ __forceinline__ void run_env(const StepArgs& a, const StepCtx* ctx, i
 // stores of run_env's one-wave loop, from the state wave's published post-step state; at the end the episode
 // fields and the fused statistics.  Same functions (obs_reward, emit / emit_env) on the same values: the
 // outputs are bitwise those of the one-wave rollout.
-template <bool CLS, bool PLAIN = false>
+template <bool CLS, bool PLAIN = false, bool WT = false>
 __device__ __forceinline__ void out_wave(const StepArgs& a, const StepCtx* ctx, int K, const OutPtrs* outs,
                                          size_t out_stride, float* wave_lds, int i, int e, bool valid, int task,
                                          int stats_mode, LaneStats* ls, OutRingLds& R) {
@@ -461,7 +486,10 @@ __device__ __forceinline__ void out_wave(const StepArgs& a, const StepCtx* ctx, 
         emit_env(o, e, vout, ob, rew, rs, to, false);
         if (k == K - 1) emit_env(outs[1], e, vout, ob, rew, rs, to, false);
       } else {
-        emit(o, wave_lds, i, a.n, vout, ob, rew, rs, to, false);
+        // WT: written through, but for the last step's row: its acknowledgements would land in the tail, behind
+        // reduce_stats' vmcnt(0) drain, and cost more there than 65 x n bytes add to the writeback
+        if (WT && k + 1 < K) emit<true>(o, wave_lds, i, a.n, vout, ob, rew, rs, to, false);
+        else emit(o, wave_lds, i, a.n, vout, ob, rew, rs, to, false);
         if (k == K - 1) emit(outs[1], wave_lds, i, a.n, vout, ob, rew, rs, to, false);
       }
     } else if (CLS) {
@@ -747,7 +775,10 @@ __device__ __forceinline__ void step_body(const StepArgs& a, const StepCtx* ctx,
       if (run_task == OUZ_TASK_TRACKING || run_task == OUZ_TASK_EKF_LEE_LANDED)
         cov_wave(a, ctx, K, i, e, valid, *spl);
     } else if (OWV && role == kOutRole) {
-      out_wave<CLS, PLAIN>(a, ctx, K, outs, out_stride, wave_lds, i, e, valid, run_task, sm, &ls, *orl);
+      // the storage rows written through in the plain LeeLanded kernel alone, by measurement: LeeLanded gained with
+      // them at 4096 and at 8192 envs, QuadFault lost 4.5 % at both (docs/HISTORY.md round 18)
+      out_wave<CLS, PLAIN, PLAIN && TASK == OUZ_TASK_LEE_LANDED>(a, ctx, K, outs, out_stride, wave_lds, i, e, valid,
+                                                                 run_task, sm, &ls, *orl);
       if (sm) reduce_stats(*rst, blockIdx.x, gridDim.x, ls);   // the output waves of the exact grid
     }
     return;
