@@ -41,6 +41,67 @@ namespace ouz {
 
 enum Ctrl { CTRL_RL = 0, CTRL_LEE_TRUE = 1, CTRL_LEE_EST = 2 };
 enum TargetMode { TGT_GOAL = 0, TGT_PLATFORM = 1, TGT_TRAJ = 2 };
+
+// The form of a step / rollout kernel's per-env code: one unsigned of named bits, handed down from the kernel
+// (step_body) through run_env / out_wave.  What follows from several bits, or from a bit and the task, is derived below.
+constexpr unsigned F_NONE = 0u;   // the one-wave VecTask.step in env order
+// MULTI: K steps in one launch (the rollouts: load once, K x (step + emit), store once); without it the single
+//   VecTask.step kernel (K = 1, no loop, no rollout storage), which keeps the register budget of one step.
+constexpr unsigned F_MULTI = 1u << 0;
+// PRE: pre_physics_step only (ouz_pre_physics): stop before the integrator and write the body wrench [6] (force,
+//   torque; body frame at the COM) that gym.simulate would integrate to `wrench`.
+constexpr unsigned F_PRE = 1u << 1;
+// CLS: the slots are not in env order (the class layouts, the host build): the env index e keys the RNG and indexes
+//   the env-order buffers, the state slot i its tile.
+constexpr unsigned F_CLS = 1u << 2;
+constexpr unsigned F_NTL = 1u << 3;   // non-temporal state loads (large N: nt_loads_default)
+// QLN: the quad-lane estimator (quad_pv_ql.h): the four lanes of a quad step the same env and split its PV covariance
+//   step, which lives in LDS at `ql`; every other part runs identically in all four, and lane 0 alone writes the
+//   env's outputs, statistics and state (the lanes 0-2 write the covariance elements they own).
+constexpr unsigned F_QLN = 1u << 4;
+// SPW: the state wave of the split-wave estimator rollout (quad_pv_split.h): the covariance is stepped by the
+//   workgroup's other wave (cov_wave), the two meet in `spl_lds`.
+constexpr unsigned F_SPW = 1u << 5;
+// OWV: the state wave of a rollout with an output wave (out_wave): the step stops at the done decision and publishes
+//   the post-step state into `orl` (its target through *post_target); observation, reward, episode tracking and
+//   statistics are the output wave's, so env_core writes no `ob` / `rew`.
+constexpr unsigned F_OWV = 1u << 6;
+// PLAIN: a plain-config launch (plain_config): what that predicate fixes (no physical DR: the scales are the constant
+//   1) is a constant instead of a load, a select or a branch on StepArgs; the arithmetic that remains is the general
+//   form's, operation for operation (a scale that is the constant 1 multiplies exactly).
+constexpr unsigned F_PLAIN = 1u << 7;
+constexpr unsigned F_MIXT = 1u << 8;   // one task's launch of the split mixed curriculum (mixed_task_tile)
+constexpr bool has(unsigned form, unsigned bit) { return (form & bit) != 0u; }
+
+// The legal forms: what each bit requires of the others (of the controller or the task: run_env, step_body).
+template <unsigned FORM>
+constexpr bool form_checked() {
+  static_assert(!has(FORM, F_SPW | F_OWV) || (has(FORM, F_MULTI) && !has(FORM, F_PRE | F_QLN)),
+                "the multi-wave forms (split wave, output wave) are the rollout's");
+  static_assert(!has(FORM, F_PLAIN) || (has(FORM, F_OWV) && !has(FORM, F_SPW | F_CLS)),
+                "the plain form is the output-wave rollout's, identity layout");
+  static_assert(!has(FORM, F_MIXT) || !has(FORM, F_CLS), "a task launch of the mixed curriculum's identity layout");
+  return true;
+}
+#ifndef OUZ_CARRY_R
+#define OUZ_CARRY_R 1   // 0: an A/B build that forms R(q) twice per step as the one-step kernels do (bitwise the same)
+#endif
+// CARRY: the state wave of an output-wave rollout hands R(q) from a step's integrator to the next step's controller
+// (the second quat_to_mat of the same quaternion was on its one dependent chain: LeeLanded 4096 envs 1.37 -> 1.30 us
+// per step).  *Rc holds it on entry to env_core (run_env forms the first step's) and the post-step one on return.
+constexpr bool form_carry(unsigned form, int ctrl) { return OUZ_CARRY_R != 0 && has(form, F_OWV) && ctrl != CTRL_LEE_EST; }
+// The plain LeeLanded rollout alone: env_core's kRare hints, and the storage rows written through, by measurement:
+// LeeLanded gained with them at 4096 and at 8192 envs, QuadFault lost 4.5 % at both (docs/HISTORY.md round 18).
+constexpr bool form_rare(unsigned form, int ctrl) { return has(form, F_PLAIN) && ctrl == CTRL_LEE_TRUE; }
+constexpr bool form_write_through(unsigned form, int task) { return has(form, F_PLAIN) && task == OUZ_TASK_LEE_LANDED; }
+// The part of a form that each leaf reads: callers instantiate it on that part alone (it asserts so), and forms that
+// differ elsewhere share one instantiation.  F_QLN in load_form / store_form: the PV covariance is not in registers.
+constexpr unsigned actions_form(unsigned f) { return f & F_CLS; }
+constexpr unsigned load_form(unsigned f) { return (f & (F_CLS | F_NTL | F_PLAIN)) | (has(f, F_QLN | F_SPW) ? F_QLN : 0u); }
+constexpr unsigned store_form(unsigned f) { return (f & F_OWV) | (has(f, F_QLN | F_SPW) ? F_QLN : 0u); }
+constexpr unsigned core_form(unsigned f) { return f & (F_PRE | F_QLN | F_SPW | F_OWV | F_PLAIN); }
+constexpr unsigned obs_form(unsigned f) { return f & F_PLAIN; }
+
 constexpr int kMaxBlock = 256;   // step/rollout kernel launch bound (LDS staging is sized for it)
 // At or below this many envs a launch has at most 4 waves per CU and the step is latency-bound;
 // above it, bandwidth-bound (the launch grid switches from 64- to 256-lane blocks at the same size).
@@ -127,7 +188,7 @@ struct TaskParams {
   int32_t land_vs_ctrl, dr, fault, motor_yaw;
 };
 
-static TaskParams task_preset(int task) {
+constexpr TaskParams task_preset(int task) {
   TaskParams t{};
   switch (task) {
     case OUZ_TASK_OUZELUM:  // tasks/ouzelum.py, cfg/task/Ouzelum.yaml
@@ -153,6 +214,8 @@ static TaskParams task_preset(int task) {
   }
   return t;
 }
+constexpr int task_ctrl(int task) { return task_preset(task).ctrl; }
+constexpr int task_tgt(int task) { return task_preset(task).target_mode; }
 
 struct EnvConsts {
   float dt, thrust_step, thrust_max, plat_speed, dr_lo, dr_hi, fault_eta_hi, wmax;
@@ -540,27 +603,27 @@ struct EnvRegs {
 };
 
 // One env's action row (vec_task.py:313: actions (N, 4) f32 on rl_device): a 16-byte load per lane.
-// CLS: the slot layout is not env order (the mixed curriculum's class layout): the row of env e.
-template <int CTRL, int TGT, bool CLS = false>
+// CLS: the row of env e.
+template <int CTRL, int TGT, unsigned FORM = 0u>
 OUZ_DEV void load_actions(const float* actions, EnvRegs<CTRL, TGT>& S, int e = 0) {
+  static_assert(FORM == actions_form(FORM), "instantiate on actions_form(FORM)");
   if constexpr (CTRL == CTRL_RL) {
-    if constexpr (CLS) S.act = reinterpret_cast<const float4*>(actions)[e];
+    if constexpr (has(FORM, F_CLS)) S.act = reinterpret_cast<const float4*>(actions)[e];
     else S.act = reinterpret_cast<const float4*>(actions + (size_t)S.T.first * OUZ_NUM_ACT)[S.T.l];
   }
 }
 
-// QLN: the quad-lane estimator (quad_pv_ql.h): the PV covariance goes to LDS (pv_lds_load), not to registers.
-// PLAIN: a plain-config launch (plain_config): no physical DR, the scales are the constant 1.
-template <int CTRL, int TGT, bool CLS = false, bool NTL = false, bool QLN = false, bool PLAIN = false>
+template <int CTRL, int TGT, unsigned FORM = 0u>
 OUZ_DEV void env_load(const StepArgs& a, int i, const TaskParams& tp, EnvRegs<CTRL, TGT>& S,
                                          const float* actions) {
+  static_assert(FORM == load_form(FORM), "instantiate on load_form(FORM)");
+  constexpr bool CLS = has(FORM, F_CLS), NTL = has(FORM, F_NTL), PLAIN = has(FORM, F_PLAIN);
   // reset_buf and time_outs are read unconditionally and combined without a branch, so the two flag
   // loads and the state loads below are in flight together (one memory round trip, not three:
   // a short-circuit `!rst && timeouts == 0` made the time-out load wait for the reset load).
   // i: env index (the class layout's env-order buffers are not lane-contiguous)
   const int64_t rv = CLS ? a.rst_in[i] : (a.rst_in + S.T.first)[S.T.l];
   const uint32_t tv = CLS ? a.to_in[i] : (a.to_in + S.T.first)[S.T.l];
-  // NTL: non-temporal state loads (large N: see nt_loads_default)
   const auto L = [&](int f) -> float { return NTL ? ld_nt(S.T, f) : ld(S.T, f); };
   const auto LI = [&](int f) -> int32_t { return NTL ? ldi_nt(S.T, f) : ldi(S.T, f); };
   const auto L3 = [&](int f) -> V3 { return v3(L(f), L(f + 1), L(f + 2)); };
@@ -590,7 +653,7 @@ OUZ_DEV void env_load(const StepArgs& a, int i, const TaskParams& tp, EnvRegs<CT
     if (tp.fault) { S.frot = LI(OUZ_I_FAULT_ROTOR); S.fonset = LI(OUZ_I_FAULT_ONSET); S.eta = L(OUZ_F_FAULT_ETA); }
     // in flight with the state loads: issued inside the step it would be a second memory round trip
     // behind the reset branch (every wave's critical path, and half the bytes in flight at large N)
-    load_actions<CTRL, TGT, CLS>(actions, S, i);
+    load_actions<CTRL, TGT, actions_form(FORM)>(actions, S, i);
   }
   if constexpr (CTRL == CTRL_LEE_EST) {
     S.prev_v = L3(OUZ_F_PREV_V);
@@ -600,7 +663,7 @@ OUZ_DEV void env_load(const StepArgs& a, int i, const TaskParams& tp, EnvRegs<CT
     for (int k = 0; k < 10; ++k) S.eP[k] = L(OUZ_F_EKF_P + k);
 #pragma unroll
     for (int k = 0; k < 9; ++k) S.px[k] = L(OUZ_F_PV_X + k);
-    if constexpr (!QLN) {
+    if constexpr (!has(FORM, F_QLN)) {
 #pragma unroll
       for (int k = 0; k < 45; ++k) S.pP[k] = L(OUZ_F_PV_P + k);
     }
@@ -621,9 +684,10 @@ OUZ_DEV void env_load(const StepArgs& a, int i, const TaskParams& tp, EnvRegs<CT
   S.flags_clear = (rv == 0) & (tv == 0u) & (a.rst_in == a.reset);
 }
 
-// EPW: this wave owns the episode-tracking fields (false for the state wave of a rollout with an output wave)
-template <int CTRL, int TGT, bool QLN = false, bool EPW = true>
+template <int CTRL, int TGT, unsigned FORM = 0u>
 OUZ_DEV void env_store(const StepArgs& a, int i, const TaskParams& tp, const EnvRegs<CTRL, TGT>& S) {
+  static_assert(FORM == store_form(FORM), "instantiate on store_form(FORM)");
+  constexpr bool EPW = !has(FORM, F_OWV);   // this wave owns the episode-tracking fields (else: the output wave)
   st3(S.T, OUZ_F_P, S.p);
   st(S.T, OUZ_F_Q, S.q.x); st(S.T, OUZ_F_Q + 1, S.q.y); st(S.T, OUZ_F_Q + 2, S.q.z); st(S.T, OUZ_F_Q + 3, S.q.w);
   st3(S.T, OUZ_F_V, S.v);
@@ -659,7 +723,7 @@ OUZ_DEV void env_store(const StepArgs& a, int i, const TaskParams& tp, const Env
     for (int k = 0; k < 10; ++k) st(S.T, OUZ_F_EKF_P + k, S.eP[k]);
 #pragma unroll
     for (int k = 0; k < 9; ++k) st(S.T, OUZ_F_PV_X + k, S.px[k]);
-    if constexpr (!QLN) {
+    if constexpr (!has(FORM, F_QLN)) {
 #pragma unroll
       for (int k = 0; k < 45; ++k) st(S.T, OUZ_F_PV_P + k, S.pP[k]);
     }
@@ -723,16 +787,17 @@ OUZ_DEV void platform_step(const StepArgs& a, const StepCtx& sc, uint32_t gid,
 
 // compute_observations + compute_ingenuity_reward of the post-step state (ekf_lee_landed.py:653-723,
 // vec_task.py:351-353): one body for the one-wave step and the output wave (out_wave).
-template <bool PLAIN = false>
+template <unsigned FORM = 0u>
 OUZ_DEV void obs_reward(const StepArgs& a, const StepCtx& sc, const TaskParams& tp, int task,
                                            uint32_t gid, V3 p, Q4 q, V3 v, V3 w, V3 target, float* ob, float& rew,
                                            float& dist) {
+  static_assert(FORM == obs_form(FORM), "instantiate on obs_form(FORM)");
   ob[0] = (target.x - p.x) / 3.0f; ob[1] = (target.y - p.y) / 3.0f; ob[2] = (target.z - p.z) / 3.0f;
   ob[3] = q.x; ob[4] = q.y; ob[5] = q.z; ob[6] = q.w;
   ob[7] = v.x * 0.5f; ob[8] = v.y * 0.5f; ob[9] = v.z * 0.5f;
   ob[10] = w.x / kPiF; ob[11] = w.y / kPiF; ob[12] = w.z / kPiF;
   pomdp_apply<13>(ob, tp, task, a, sc, gid, SITE_OBS, false);
-  if (!PLAIN && (a.drn_mask & 1)) dr_noise_apply<13>(ob, a.drn[0], a.seed, gid, sc.step, RNG_DRN_OBS);   // vec_task.py:351-352
+  if (!has(FORM, F_PLAIN) && (a.drn_mask & 1)) dr_noise_apply<13>(ob, a.drn[0], a.seed, gid, sc.step, RNG_DRN_OBS);   // vec_task.py:351-352
 #pragma unroll
   for (int k = 0; k < 13; ++k) ob[k] = fminf(fmaxf(ob[k], -5.0f), 5.0f);   // vec_task.py:353
   rew = reward(p, target, q, w, dist);
@@ -741,25 +806,14 @@ OUZ_DEV void obs_reward(const StepArgs& a, const StepCtx& sc, const TaskParams& 
 // ---------------------------------------------------------------------------
 // One VecTask.step of one env on register state (mirrors oracle/quad_oracle.py::OracleEnv.step)
 // ---------------------------------------------------------------------------
-// PRE: pre_physics_step only (ouz_pre_physics) -- stop before the integrator and write the body wrench
-// [6] (force, torque; body frame at the COM) that gym.simulate would integrate to `wrench`.
-// QLN: the quad-lane estimator (four lanes per env, the PV covariance in LDS at `ql`).
-// SPW: the state wave of the split-wave estimator (quad_pv_split.h): the covariance is the other wave's.
-// OWV: a rollout with an output wave: the step stops at the done decision; the output wave forms the
-// observation, reward and episode statistics from the post-step state (out_wave), so `ob` / `rew` are not
-// written here and the step's target goes to *post_target.
-// PLAIN: a plain-config launch (plain_config): what that predicate fixes is a constant here instead of a load, a
-// select or a branch on StepArgs; the arithmetic of the path that remains is the general form's, operation for
-// operation (a scale that is the constant 1 multiplies exactly).
-// CARRY: *Rc holds quat_to_mat(S.q) on entry (the fused rollout's previous step formed it for the world-frame body
-// rate, run_env before the first step) and of the post-step quaternion on return: the same function of the same
-// quaternion as forming it here, without the second evaluation on the step's dependent chain.
-template <int CTRL, int TGT, bool PRE = false, bool QLN = false, bool SPW = false, bool OWV = false,
-          bool PLAIN = false, bool CARRY = false>
+template <int CTRL, int TGT, unsigned FORM = 0u>
 OUZ_DEV void env_core(const StepArgs& a, const StepCtx& sc, int i, uint32_t gid, int task,
                                          EnvRegs<CTRL, TGT>& S, float* ob, float& rew, bool& rs, bool& timeout,
                                          float* wrench = nullptr, const PvQl* ql = nullptr,
                                          const SplitLane* spl = nullptr, V3* post_target = nullptr, M3* Rc = nullptr) {
+  constexpr bool PRE = has(FORM, F_PRE), QLN = has(FORM, F_QLN), SPW = has(FORM, F_SPW), OWV = has(FORM, F_OWV),
+                 PLAIN = has(FORM, F_PLAIN), CARRY = form_carry(FORM, CTRL);
+  static_assert(FORM == core_form(FORM), "instantiate on core_form(FORM)");
   static_assert(!CARRY || (!PRE && CTRL != CTRL_LEE_EST), "R(q) is carried by the rollouts of the tasks without the estimator");
   const TaskParams& tp = a.tp[tp_slot(task)];
   const EnvConsts& c = a.c;
@@ -780,7 +834,7 @@ OUZ_DEV void env_core(const StepArgs& a, const StepCtx& sc, int i, uint32_t gid,
   // lanes).  The per-lane test inside is the general form's.  Not for the RL tasks: under random actions some lane
   // of most QuadFault tiles resets or sits at the body-rate clamp in most steps, and the out-of-line blocks cost
   // their taken branches (8192 envs: -4.7 % env-steps/s with both hints on).
-  constexpr bool kRare = PLAIN && CTRL == CTRL_LEE_TRUE;
+  constexpr bool kRare = form_rare(FORM, CTRL);
 #ifdef OUZ_HOST
   const bool any_rst = true;
 #else
@@ -1069,7 +1123,7 @@ OUZ_DEV void env_core(const StepArgs& a, const StepCtx& sc, int i, uint32_t gid,
     dist = target_dist(p, target);
     *post_target = target;
   } else {
-    obs_reward<PLAIN>(a, sc, tp, task, gid, p, q, v, w, target, ob, rew, dist);
+    obs_reward<obs_form(FORM)>(a, sc, tp, task, gid, p, q, v, w, target, ob, rew, dist);
   }
   const bool timeout_len = S.progress >= tp.max_ep - 1;
   const bool die = dist > 8.0f || p.z < tp.z_die;

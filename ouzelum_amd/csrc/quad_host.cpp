@@ -47,7 +47,7 @@ inline void host_env_step(const StepArgs& a, const StepCtx& sc, int i, int e, in
   const uint32_t gid = a.env_offset + (uint32_t)e;
   EnvRegs<CTRL, TGT> S;
   S.T = tile_of(a, i);
-  env_load<CTRL, TGT, /*CLS: env-order buffers by env index*/ true>(a, e, tp, S, sc.actions);
+  env_load<CTRL, TGT, F_CLS>(a, e, tp, S, sc.actions);   // CLS: env-order buffers by env index
   const bool did_reset = S.rst, flags_clear = S.flags_clear;
   float ob[OUZ_NUM_OBS];
   float rew = 0.0f;

@@ -199,13 +199,6 @@ constexpr bool kPlainDefault = true;
 __host__ __device__ constexpr bool plain_task(int task) {
   return task == OUZ_TASK_LEE_LANDED || task == OUZ_TASK_OUZELUM || task == OUZ_TASK_FAULT;
 }
-// R(q) carried from a step's integrator to the next step in the output-wave rollouts (run_env CARRY);
-// -DOUZ_CARRY_R=0 forms it twice per step as the one-step kernels do (an A/B build, bitwise the same results;
-// LeeLanded 4096 envs 1.37 -> 1.30 us per step).
-#ifndef OUZ_CARRY_R
-#define OUZ_CARRY_R 1
-#endif
-constexpr bool kCarryR = OUZ_CARRY_R != 0;
 
 // The output wave of a latency-regime rollout.  The step's observation, reward, episode
 // statistics and output stores feed nothing the next step computes but the done flags, so a second wave of the
@@ -246,31 +239,23 @@ __device__ __forceinline__ void trace_count(const StepArgs& a, uint32_t step, bo
   if (e == 0) a.trace_resets[(step + 32u) % (uint32_t)a.trace_cap] = 0u;
 }
 
-// K steps of one env: load once, K x (step + emit), store once.  MULTI = false is the single
-// VecTask.step kernel (K = 1, no loop, no rollout storage) and keeps the register budget of one step.
 // Episode statistics of one lane, reduced over the grid by the fused rollout (RolloutStats).
 struct LaneStats {
   double sum, cnt, len;
 };
 
-// i: state slot (its wave tile is wave-uniform); e: env index (== i except under the trigger-class layout,
-// CLS), which keys the RNG and indexes the env-order buffers.
-// QLN: the quad-lane estimator (quad_pv_ql.h, latency-regime estimator kernels): the four lanes of a quad step
-// the same env (same slot i and env e) and split its PV covariance step; every other part of the step runs
-// identically in all four, and lane 0 of the quad alone writes the env's outputs, statistics and state
-// (the lanes 0-2 write the covariance elements they own).
-// SPW: the state wave of the split-wave estimator rollout (quad_pv_split.h; MULTI only): the covariance is
-// stepped by the workgroup's other wave (cov_wave), the two meet in `spl_lds`.
-// OWV: the state wave of a rollout with an output wave (out_wave): the step's outputs, episode tracking and
-// statistics are the output wave's; this wave publishes the post-step state into `orl` instead.
-// PLAIN: a plain-config launch (plain_config, quad_env.h; the output-wave rollouts of the tasks without the estimator).
-template <int CTRL, int TGT, bool MULTI, bool PRE = false, bool CLS = false, bool NTL = false, bool QLN = false,
-          bool SPW = false, bool OWV = false, bool PLAIN = false>
+// K steps of one env: load once, K x (step + emit), store once (FORM: the F_* bits of quad_env.h).
+// i: state slot (its wave tile is wave-uniform); e: env index (== i except under CLS).
+template <int CTRL, int TGT, unsigned FORM>
 __device__ __forceinline__ void run_env(const StepArgs& a, const StepCtx* ctx, int K, const OutPtrs* outs,
                                         size_t out_stride, float* wave_lds, int i, int e, bool valid, int task,
                                         bool direct = false, int stats_mode = 0, LaneStats* ls = nullptr,
                                         float* wrench = nullptr, SplitPvLds* spl_lds = nullptr,
                                         OutRingLds* orl = nullptr) {
+  static_assert(form_checked<FORM>());
+  constexpr bool MULTI = has(FORM, F_MULTI), PRE = has(FORM, F_PRE), CLS = has(FORM, F_CLS), QLN = has(FORM, F_QLN),
+                 SPW = has(FORM, F_SPW), OWV = has(FORM, F_OWV), PLAIN = has(FORM, F_PLAIN),
+                 CARRY = form_carry(FORM, CTRL);
   const TaskParams& tp = a.tp[tp_slot(task)];
   const uint32_t gid = a.env_offset + (uint32_t)e;
   // the env's outputs / statistics / state writes: every lane, or lane 0 of the quad
@@ -278,12 +263,8 @@ __device__ __forceinline__ void run_env(const StepArgs& a, const StepCtx* ctx, i
   const bool vout = valid && lead;
   PvQl ql{};
   SplitLane spl{spl_lds, 0, threadIdx.x & 63u};
-  static_assert(!SPW || (MULTI && !PRE && !QLN && CTRL == CTRL_LEE_EST), "the split form is the estimator rollout's");
-  static_assert(!OWV || (MULTI && !PRE && !QLN), "the output wave is the rollout's");
-  static_assert(!PLAIN || (OWV && !CLS && CTRL != CTRL_LEE_EST), "the plain form is the output-wave rollout's");
-  // The state wave of an output-wave rollout carries R(q) from a step's integrator to the next step's controller
-  // (env_core CARRY): its loop is one dependent chain, and the second quat_to_mat of the same quaternion was on it.
-  constexpr bool CARRY = kCarryR && OWV && CTRL != CTRL_LEE_EST;
+  static_assert(!SPW || CTRL == CTRL_LEE_EST, "the split form is the estimator rollout's");
+  static_assert(!PLAIN || CTRL != CTRL_LEE_EST, "the plain form is the output-wave rollout's of the tasks without the estimator");
   if constexpr (QLN) {
     static_assert(CTRL == CTRL_LEE_EST, "the quad-lane form is the estimator's");
     __shared__ double s_pv[16 * kPvLdsEnv];   // one 64-lane block = one wave = 16 envs
@@ -304,7 +285,7 @@ __device__ __forceinline__ void run_env(const StepArgs& a, const StepCtx* ctx, i
     ep_cnt_old = ldi(S.T, OUZ_I_EP_CNT);
     ep_len_old = ldi(S.T, OUZ_I_EP_LEN);
   }
-  if (valid) env_load<CTRL, TGT, CLS, NTL, QLN || SPW, PLAIN>(a, e, tp, S, ctx[0].actions);
+  if (valid) env_load<CTRL, TGT, load_form(FORM)>(a, e, tp, S, ctx[0].actions);
   if constexpr (QLN) {
     if (valid) pv_lds_load(ql, [&](int f) { return ld(S.T, OUZ_F_PV_P + f); });
     ql_sync();
@@ -317,7 +298,7 @@ __device__ __forceinline__ void run_env(const StepArgs& a, const StepCtx* ctx, i
     float rew = 0.0f;
     bool rs = false, to = false;
     const bool did_reset = vout && S.rst;
-    if (valid) env_core<CTRL, TGT, true, QLN>(a, ctx[0], e, gid, task, S, ob, rew, rs, to, wrench, &ql);
+    if (valid) env_core<CTRL, TGT, core_form(FORM)>(a, ctx[0], e, gid, task, S, ob, rew, rs, to, wrench, &ql);
     if (did_reset) a.reset[e] = 0;
   } else if constexpr (!MULTI) {
     float ob[OUZ_NUM_OBS];
@@ -325,7 +306,7 @@ __device__ __forceinline__ void run_env(const StepArgs& a, const StepCtx* ctx, i
     bool rs = false, to = false;
     const bool did_reset = vout && S.rst;
     const bool flags_clear = vout && S.flags_clear;
-    if (valid) env_core<CTRL, TGT, false, QLN>(a, ctx[0], e, gid, task, S, ob, rew, rs, to, nullptr, &ql);
+    if (valid) env_core<CTRL, TGT, core_form(FORM)>(a, ctx[0], e, gid, task, S, ob, rew, rs, to, nullptr, &ql);
     trace_count(a, ctx[0].step, did_reset, i, e);
     OUZ_STAMP(5, false);
     if (CLS) emit_env(outs[1], e, vout, ob, rew, rs, to, flags_clear);
@@ -356,10 +337,9 @@ __device__ __forceinline__ void run_env(const StepArgs& a, const StepCtx* ctx, i
       spl.k = k;
       V3 post_target = v3(0.0f, 0.0f, 0.0f);
       if (valid)
-        env_core<CTRL, TGT, false, QLN, SPW, OWV, PLAIN, CARRY>(a, ctx[k], e, gid, task, S, ob, rew, rs, to, nullptr,
-                                                                &ql, &spl, &post_target, &Rc);
+        env_core<CTRL, TGT, core_form(FORM)>(a, ctx[k], e, gid, task, S, ob, rew, rs, to, nullptr, &ql, &spl, &post_target, &Rc);
       if (kStampSlots > 13 && k == 8) OUZ_STAMP(30, false);
-      if (valid && k + 1 < K) load_actions<CTRL, TGT, CLS>(ctx[k + 1].actions, S, e);   // next step's row, before emit
+      if (valid && k + 1 < K) load_actions<CTRL, TGT, actions_form(FORM)>(ctx[k + 1].actions, S, e);   // next step's row, before emit
       if constexpr (OWV) {   // (the reset counts of the trajectory log are the output wave's)
         out_publish(*orl, k, out_seen, S.p, S.q, S.v, S.w, post_target, S.progress, rs, to, fc0, rst0);
           if (kStampSlots > 13 && k == 8) OUZ_STAMP(31, false);
@@ -410,7 +390,7 @@ __device__ __forceinline__ void run_env(const StepArgs& a, const StepCtx* ctx, i
       S.ep_cnt_add = 0;   // env_store: no accumulator atomics
     }
   }
-  if (vout) env_store<CTRL, TGT, QLN || SPW, !OWV>(a, i, tp, S);
+  if (vout) env_store<CTRL, TGT, store_form(FORM)>(a, i, tp, S);
   if constexpr (QLN) {
     if (valid) pv_lds_store(ql, [&](int f, float v) { st(S.T, OUZ_F_PV_P + f, v); });
   }
@@ -422,10 +402,11 @@ __device__ __forceinline__ void run_env(const StepArgs& a, const StepCtx* ctx, i
 // stores of run_env's one-wave loop, from the state wave's published post-step state; at the end the episode
 // fields and the fused statistics.  Same functions (obs_reward, emit / emit_env) on the same values: the
 // outputs are bitwise those of the one-wave rollout.
-template <bool CLS, bool PLAIN = false, bool WT = false>
+template <unsigned FORM, bool WT>
 __device__ __forceinline__ void out_wave(const StepArgs& a, const StepCtx* ctx, int K, const OutPtrs* outs,
                                          size_t out_stride, float* wave_lds, int i, int e, bool valid, int task,
                                          int stats_mode, LaneStats* ls, OutRingLds& R) {
+  constexpr bool CLS = has(FORM, F_CLS), PLAIN = has(FORM, F_PLAIN);
   const TaskParams& tp = a.tp[tp_slot(task)];
   const uint32_t gid = a.env_offset + (uint32_t)e, lane = threadIdx.x & 63u;
   const Tile T = tile_of(a, i);
@@ -469,7 +450,7 @@ __device__ __forceinline__ void out_wave(const StepArgs& a, const StepCtx* ctx, 
         t[6] = v.x; t[7] = v.y; t[8] = v.z;
       }
       float dist;
-      obs_reward<PLAIN>(a, ctx[k], tp, task, gid, p, q, v, w, target, ob, rew, dist);
+      obs_reward<obs_form(FORM)>(a, ctx[k], tp, task, gid, p, q, v, w, target, ob, rew, dist);
       if (a.track_episodes) {   // RecordEpisodeStatisticsTorch.step (PPO/utils.py:20-35), as env_core
         ep_ret += rew;
         if (rs) { ep_sum_add += ep_ret; ep_cnt_add += 1; ep_len_add += progress; ep_ret = 0.0f; }
@@ -601,7 +582,6 @@ __device__ __forceinline__ void prefetch_kernargs() {
                    "s"(t[8]), "s"(t[9]), "s"(t[10]), "s"(t[11]), "s"(t[12]), "s"(t[13]), "s"(t[14]), "s"(t[15]));
 }
 
-// The step kernel body: one env per lane, K steps (MULTI) or one.
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
@@ -691,24 +671,55 @@ __device__ __forceinline__ int mixed_task_tile(const StepArgs& a, int task, int 
   return (t >= 0 && t < (int64_t)((a.n + 63) / 64)) ? (int)t : -1;
 }
 
-template <int TASK, bool MULTI, bool PRE = false, bool CLS = false, bool NTL = false, bool QUAD = false,
-          bool SPW = false, bool OWV = false, bool MIXT = false, bool PLAIN = false>
+// The env (a.n: an idle slot) held by state slot i.
+template <int TASK, unsigned FORM>
+__device__ __forceinline__ int slot_to_env(const StepArgs& a, int i) {
+  if constexpr (has(FORM, F_CLS) && TASK == OUZ_TASK_MIXED) {
+    const int64_t e64 = mixed_slot_env(a.env_offset, i);
+    return (e64 >= 0 && e64 < a.n) ? (int)e64 : a.n;
+  } else if constexpr (has(FORM, F_CLS)) {
+    return slot_env(i);
+  }
+  return i;
+}
+// The mixed curriculum's class layout: the 1344-id chunk (one task) that 64-slot tile `tile` lies in.
+#define OUZ_CHUNK_OF_TILE(a, tile) ((a).env_offset / kClassBlock + (uint32_t)((tile) * 64) / kClassBlock)
+// One chunk task's form in the mixed curriculum's class layout: split wave and quad lane are QuadTracking's alone.
+constexpr unsigned chunk_form(unsigned form, int task) {
+  return task == OUZ_TASK_TRACKING ? form : form & ~(F_SPW | F_QLN);
+}
+// step_body: the per-env code of task T (a constant) in form F for this lane; below it, for the mixed curriculum's
+// class layout, the wave-uniform chunk task t (a variable) as A, B or else C
+#define OUZ_RUN_ENV(T, F, valid, direct)                                                                          \
+  run_env<task_ctrl(T), task_tgt(T), (F) & ~F_MIXT>(a, ctx, K, outs, out_stride, wave_lds, i, e, valid, T, direct, sm, \
+                                                    &ls, wrench, spl, orl)
+#define OUZ_RUN_CHUNK(t, valid, A, B, C)                                  \
+  if (t == A) OUZ_RUN_ENV(A, chunk_form(FORM, A), valid, false);          \
+  else if (t == B) OUZ_RUN_ENV(B, chunk_form(FORM, B), valid, false);     \
+  else OUZ_RUN_ENV(C, chunk_form(FORM, C), valid, false)
+
+// The step kernel body: one env per lane, K steps (MULTI) or one.
+template <int TASK, unsigned FORM>
 __device__ __forceinline__ void step_body(const StepArgs& a, const StepCtx* ctx, int K, const OutPtrs* outs,
                                           uint64_t out_stride, const RolloutStats* rst = nullptr,
                                           float* wrench = nullptr) {
+  static_assert(form_checked<FORM>());
+  constexpr bool MULTI = has(FORM, F_MULTI), CLS = has(FORM, F_CLS), QLN = has(FORM, F_QLN), SPW = has(FORM, F_SPW),
+                 OWV = has(FORM, F_OWV), MIXT = has(FORM, F_MIXT), PLAIN = has(FORM, F_PLAIN);
+  static_assert(!CLS || class_layout_task(TASK), "the class layout is the estimator tasks' and the curriculum's");
+  static_assert(!(SPW || QLN) || quad_lane_kernel(TASK, CLS), "the split and quad-lane forms are the estimator's class layout");
+  static_assert(!PLAIN || plain_task(TASK), "the plain form: plain_task's output-wave rollouts");
+  static_assert(!MIXT || TASK != OUZ_TASK_MIXED, "a task launch of the mixed curriculum's identity layout");
   __shared__ float4 s_obs4[kMaxBlock * OUZ_NUM_OBS / 4];
   float* wave_lds = reinterpret_cast<float*>(s_obs4) + (threadIdx.x & ~63) * OUZ_NUM_OBS;
   const int sm = (MULTI && rst) ? rst->mode : 0;
   LaneStats ls{0.0, 0.0, 0.0};
+  SplitPvLds* spl = nullptr;
+  OutRingLds* orl = nullptr;
   if constexpr (SPW || OWV) {
     // Multi-wave rollouts, one workgroup per 64-slot tile: wave 0 steps the tile's envs; with SPW (the
     // estimator's trigger-class layout, quad_pv_split.h) wave 1 steps their PV covariance; with OWV the last
     // wave forms the outputs (out_wave).
-    static_assert(MULTI && !PRE && !QUAD, "the multi-wave forms are the rollout's");
-    static_assert(!SPW || quad_lane_kernel(TASK, CLS), "the split form is the estimator's class layout");
-    static_assert(!PLAIN || (OWV && !SPW && !CLS && plain_task(TASK)), "the plain form: plain_task's output-wave rollouts");
-    SplitPvLds* spl = nullptr;
-    OutRingLds* orl = nullptr;
     if constexpr (SPW) {
       __shared__ SplitPvLds s_split;
       spl = &s_split;
@@ -730,92 +741,54 @@ __device__ __forceinline__ void step_body(const StepArgs& a, const StepCtx* ctx,
     }
     __syncthreads();
     const int tile = (int)blockIdx.x, i = tile * 64 + (int)(threadIdx.x & 63u), role = (int)(threadIdx.x >> 6);
-    int e = i;
-    int chunk_task = TASK;
+    int e = i;   // slot_to_env's mapping, written out (docs/HISTORY.md round 19)
     if constexpr (CLS && TASK == OUZ_TASK_MIXED) {
       const int64_t e64 = mixed_slot_env(a.env_offset, i);
       e = (e64 >= 0 && e64 < a.n) ? (int)e64 : a.n;
-      chunk_task = mixed_chunk_task(a.env_offset / kClassBlock + (uint32_t)(tile * 64) / kClassBlock);
     } else if constexpr (CLS) {
       e = slot_env(i);
     }
+    int chunk_task = TASK;
+    if constexpr (CLS && TASK == OUZ_TASK_MIXED) chunk_task = mixed_chunk_task(OUZ_CHUNK_OF_TILE(a, tile));
     const bool valid = e < a.n;
     const int run_task = TASK == OUZ_TASK_MIXED ? chunk_task : TASK;
     constexpr int kOutRole = SPW ? 2 : 1;
     if (role == 0) {
-      if constexpr (TASK == OUZ_TASK_OUZELUM || TASK == OUZ_TASK_FAULT)
-        run_env<CTRL_RL, TGT_GOAL, true, false, CLS, false, false, false, OWV, PLAIN>(
-            a, ctx, K, outs, out_stride, wave_lds, i, e, valid, TASK, false, sm, &ls, nullptr, nullptr, orl);
-      else if constexpr (TASK == OUZ_TASK_LEE_LANDED)
-        run_env<CTRL_LEE_TRUE, TGT_PLATFORM, true, false, CLS, false, false, false, OWV, PLAIN>(
-            a, ctx, K, outs, out_stride, wave_lds, i, e, valid, TASK, false, sm, &ls, nullptr, nullptr, orl);
-      else if constexpr (TASK == OUZ_TASK_LANDING)
-        run_env<CTRL_RL, TGT_TRAJ, true, false, CLS, false, false, false, OWV>(
-            a, ctx, K, outs, out_stride, wave_lds, i, e, valid, TASK, false, sm, &ls, nullptr, nullptr, orl);
-      else if constexpr (TASK == OUZ_TASK_EKF_LEE_LANDED)
-        run_env<CTRL_LEE_EST, TGT_PLATFORM, true, false, CLS, false, false, SPW, OWV>(
-            a, ctx, K, outs, out_stride, wave_lds, i, e, valid, TASK, false, sm, &ls, nullptr, spl, orl);
-      else if constexpr (TASK == OUZ_TASK_TRACKING)
-        run_env<CTRL_LEE_EST, TGT_TRAJ, true, false, CLS, false, false, SPW, OWV>(
-            a, ctx, K, outs, out_stride, wave_lds, i, e, valid, TASK, false, sm, &ls, nullptr, spl, orl);
-      else if constexpr (TASK == OUZ_TASK_MIXED && CLS) {
-        if (chunk_task == OUZ_TASK_TRACKING)
-          run_env<CTRL_LEE_EST, TGT_TRAJ, true, false, true, false, false, SPW, OWV>(
-              a, ctx, K, outs, out_stride, wave_lds, i, e, valid, OUZ_TASK_TRACKING, false, sm, &ls, nullptr, spl, orl);
-        else if (chunk_task == OUZ_TASK_LEE_LANDED)
-          run_env<CTRL_LEE_TRUE, TGT_PLATFORM, true, false, true, false, false, false, OWV>(
-              a, ctx, K, outs, out_stride, wave_lds, i, e, valid, OUZ_TASK_LEE_LANDED, false, sm, &ls, nullptr, nullptr,
-              orl);
-        else
-          run_env<CTRL_RL, TGT_GOAL, true, false, true, false, false, false, OWV>(
-              a, ctx, K, outs, out_stride, wave_lds, i, e, valid, OUZ_TASK_FAULT, false, sm, &ls, nullptr, nullptr, orl);
+      if constexpr (TASK != OUZ_TASK_MIXED) OUZ_RUN_ENV(TASK, FORM, valid, false);
+      else if constexpr (CLS) {
+        OUZ_RUN_CHUNK(chunk_task, valid, OUZ_TASK_TRACKING, OUZ_TASK_LEE_LANDED, OUZ_TASK_FAULT);
       }
       if (!OWV && sm) reduce_stats(*rst, blockIdx.x, gridDim.x, ls);   // the state waves of the exact grid
     } else if (SPW && role == 1) {
       if (run_task == OUZ_TASK_TRACKING || run_task == OUZ_TASK_EKF_LEE_LANDED)
         cov_wave(a, ctx, K, i, e, valid, *spl);
     } else if (OWV && role == kOutRole) {
-      // the storage rows written through in the plain LeeLanded kernel alone, by measurement: LeeLanded gained with
-      // them at 4096 and at 8192 envs, QuadFault lost 4.5 % at both (docs/HISTORY.md round 18)
-      out_wave<CLS, PLAIN, PLAIN && TASK == OUZ_TASK_LEE_LANDED>(a, ctx, K, outs, out_stride, wave_lds, i, e, valid,
-                                                                 run_task, sm, &ls, *orl);
+      out_wave<FORM, form_write_through(FORM, TASK)>(a, ctx, K, outs, out_stride, wave_lds, i, e, valid, run_task, sm, &ls, *orl);
       if (sm) reduce_stats(*rst, blockIdx.x, gridDim.x, ls);   // the output waves of the exact grid
     }
     return;
   }
-  if constexpr (QUAD && quad_lane_kernel(TASK, CLS)) {
+  if constexpr (QLN && quad_lane_kernel(TASK, CLS)) {
     // 64-lane blocks, four per tile: quarter q of tile t holds slots t*64 + q*16 .. +15, four lanes per slot
     const int tile = (int)(blockIdx.x >> 2), quarter = (int)(blockIdx.x & 3u);
     const int iq = tile * 64 + quarter * 16 + (int)(threadIdx.x >> 2);   // this quad's slot
-    bool quad = true;
+    int chunk_task = TASK;
     int i = iq;
     if constexpr (TASK == OUZ_TASK_MIXED) {
       // a tile lies in one 1344-id chunk (one task): the QuadTracking chunks run quad-lane, the other tasks
       // one lane per slot in the tile's first block (its other three exit at once)
-      const uint32_t ch = a.env_offset / kClassBlock + (uint32_t)(tile * 64) / kClassBlock;
-      quad = mixed_chunk_task(ch) == OUZ_TASK_TRACKING;
-      if (!quad) i = tile * 64 + (int)threadIdx.x;
+      chunk_task = mixed_chunk_task(OUZ_CHUNK_OF_TILE(a, tile));
+      if (chunk_task != OUZ_TASK_TRACKING) i = tile * 64 + (int)threadIdx.x;
     }
-    int e = a.n;
-    if constexpr (TASK == OUZ_TASK_MIXED) {
-      const int64_t e64 = mixed_slot_env(a.env_offset, i);
-      e = (e64 >= 0 && e64 < a.n) ? (int)e64 : a.n;
-    } else {
-      e = slot_env(i);
-    }
+    const bool quad = TASK != OUZ_TASK_MIXED || chunk_task == OUZ_TASK_TRACKING;
+    const int e = slot_to_env<TASK, FORM>(a, i);
     const bool valid = e < a.n && (quad || quarter == 0);
     if (quad) {
-      run_env<CTRL_LEE_EST, TASK == OUZ_TASK_EKF_LEE_LANDED ? TGT_PLATFORM : TGT_TRAJ, MULTI, PRE, true, false, true>(a, ctx, K, outs, out_stride, wave_lds, i, e, valid,
-                                      TASK == OUZ_TASK_MIXED ? OUZ_TASK_TRACKING : TASK, false, sm, &ls, wrench);
+      OUZ_RUN_ENV((TASK == OUZ_TASK_MIXED ? OUZ_TASK_TRACKING : TASK), FORM, valid, false);
     } else if (quarter == 0) {
       if constexpr (TASK == OUZ_TASK_MIXED) {
-        const uint32_t ch = a.env_offset / kClassBlock + (uint32_t)(tile * 64) / kClassBlock;
-        if (mixed_chunk_task(ch) == OUZ_TASK_LEE_LANDED)
-          run_env<CTRL_LEE_TRUE, TGT_PLATFORM, MULTI, PRE, true>(a, ctx, K, outs, out_stride, wave_lds, i, e, valid,
-                                                               OUZ_TASK_LEE_LANDED, false, sm, &ls, wrench);
-        else
-          run_env<CTRL_RL, TGT_GOAL, MULTI, PRE, true>(a, ctx, K, outs, out_stride, wave_lds, i, e, valid,
-                                                     OUZ_TASK_FAULT, false, sm, &ls, wrench);
+        if (chunk_task == OUZ_TASK_LEE_LANDED) OUZ_RUN_ENV(OUZ_TASK_LEE_LANDED, chunk_form(FORM, OUZ_TASK_LEE_LANDED), valid, false);
+        else OUZ_RUN_ENV(OUZ_TASK_FAULT, chunk_form(FORM, OUZ_TASK_FAULT), valid, false);
       }
     }
     if (sm) reduce_stats(*rst, blockIdx.x, gridDim.x, ls);   // every wave of the exact grid takes part
@@ -823,7 +796,6 @@ __device__ __forceinline__ void step_body(const StepArgs& a, const StepCtx* ctx,
   }
   int i = blockIdx.x * step_block_for(a.n) + threadIdx.x;   // state slot
   if constexpr (MIXT) {   // one task of the mixed curriculum: this wave's tile among that task's chunks
-    static_assert(!CLS && TASK != OUZ_TASK_MIXED, "a task launch of the mixed curriculum's identity layout");
     const int t = (int)__builtin_amdgcn_readfirstlane(
         (uint32_t)mixed_task_tile(a, TASK, (int)(blockIdx.x * (step_block_for(a.n) / 64) + (threadIdx.x >> 6))));
     i = (t < 0 ? (a.n + 63) / 64 * 64 : t * 64) + (int)(threadIdx.x & 63u);
@@ -836,37 +808,15 @@ __device__ __forceinline__ void step_body(const StepArgs& a, const StepCtx* ctx,
   }
   const int first = i - (int)(threadIdx.x & 63);
   if (first >= (CLS ? a.n_slots : a.n)) return;   // whole wave past the end
-  int e = i;                                       // env index (a.n: an idle slot)
-  if constexpr (CLS && TASK == OUZ_TASK_MIXED) {
-    const int64_t e64 = mixed_slot_env(a.env_offset, i);
-    e = (e64 >= 0 && e64 < a.n) ? (int)e64 : a.n;
-  } else if constexpr (CLS) {
-    e = slot_env(i);
-  }
+  const int e = slot_to_env<TASK, FORM>(a, i);     // env index (a.n: an idle slot)
   const bool valid = e < a.n;
-  if constexpr (TASK == OUZ_TASK_OUZELUM || TASK == OUZ_TASK_FAULT) {
-    run_env<CTRL_RL, TGT_GOAL, MULTI, PRE, false, NTL>(a, ctx, K, outs, out_stride, wave_lds, i, e, valid, TASK, false, sm, &ls, wrench);
-  } else if constexpr (TASK == OUZ_TASK_LEE_LANDED) {
-    run_env<CTRL_LEE_TRUE, TGT_PLATFORM, MULTI, PRE, false, NTL>(a, ctx, K, outs, out_stride, wave_lds, i, e, valid, TASK, false, sm, &ls, wrench);
-  } else if constexpr (TASK == OUZ_TASK_EKF_LEE_LANDED) {
-    run_env<CTRL_LEE_EST, TGT_PLATFORM, MULTI, PRE, CLS, NTL>(a, ctx, K, outs, out_stride, wave_lds, i, e, valid, TASK, false, sm, &ls, wrench);
-  } else if constexpr (TASK == OUZ_TASK_LANDING) {
-    run_env<CTRL_RL, TGT_TRAJ, MULTI, PRE, false, NTL>(a, ctx, K, outs, out_stride, wave_lds, i, e, valid, TASK, false, sm, &ls, wrench);
-  } else if constexpr (TASK == OUZ_TASK_TRACKING) {
-    run_env<CTRL_LEE_EST, TGT_TRAJ, MULTI, PRE, CLS, NTL>(a, ctx, K, outs, out_stride, wave_lds, i, e, valid, TASK, false, sm, &ls, wrench);
+  if constexpr (TASK != OUZ_TASK_MIXED) {
+    OUZ_RUN_ENV(TASK, FORM, valid, false);
   } else if constexpr (CLS) {
     // mixed curriculum, class layout: a wave's slots lie in one 1344-id chunk, so its task is wave-uniform
     const uint32_t c = a.env_offset / kClassBlock + __builtin_amdgcn_readfirstlane((uint32_t)first) / kClassBlock;
     const int t = mixed_chunk_task(c);
-    if (t == OUZ_TASK_LEE_LANDED)
-      run_env<CTRL_LEE_TRUE, TGT_PLATFORM, MULTI, PRE, true>(a, ctx, K, outs, out_stride, wave_lds, i, e, valid,
-                                                           OUZ_TASK_LEE_LANDED, false, sm, &ls, wrench);
-    else if (t == OUZ_TASK_TRACKING)
-      run_env<CTRL_LEE_EST, TGT_TRAJ, MULTI, PRE, true>(a, ctx, K, outs, out_stride, wave_lds, i, e, valid,
-                                                      OUZ_TASK_TRACKING, false, sm, &ls, wrench);
-    else
-      run_env<CTRL_RL, TGT_GOAL, MULTI, PRE, true>(a, ctx, K, outs, out_stride, wave_lds, i, e, valid, OUZ_TASK_FAULT,
-                                                 false, sm, &ls, wrench);
+    OUZ_RUN_CHUNK(t, valid, OUZ_TASK_LEE_LANDED, OUZ_TASK_TRACKING, OUZ_TASK_FAULT);
   } else {
     // Per-lane task; each task's lanes run in turn.  When the shard offset is a multiple of 64 the
     // curriculum's 64-env blocks coincide with waves and exactly one branch runs per wave.  Both
@@ -875,36 +825,34 @@ __device__ __forceinline__ void step_body(const StepArgs& a, const StepCtx* ctx,
     const bool direct = (a.env_offset & 63) != 0;   // a wave straddles two blocks: no LDS obs staging
     const bool vl = valid && t == OUZ_TASK_LEE_LANDED, vt = valid && t == OUZ_TASK_TRACKING;
     const bool vr = valid && !vl && !vt;
-    if (__any(vl))
-      run_env<CTRL_LEE_TRUE, TGT_PLATFORM, MULTI, PRE, false, NTL>(a, ctx, K, outs, out_stride, wave_lds, i, i, vl,
-                                                  OUZ_TASK_LEE_LANDED, direct, sm, &ls, wrench);
-    if (__any(vt))
-      run_env<CTRL_LEE_EST, TGT_TRAJ, MULTI, PRE, false, NTL>(a, ctx, K, outs, out_stride, wave_lds, i, i, vt,
-                                             OUZ_TASK_TRACKING, direct, sm, &ls, wrench);
-    if (__any(vr))
-      run_env<CTRL_RL, TGT_GOAL, MULTI, PRE, false, NTL>(a, ctx, K, outs, out_stride, wave_lds, i, i, vr, OUZ_TASK_FAULT,
-                                        direct, sm, &ls, wrench);
+    if (__any(vl)) OUZ_RUN_ENV(OUZ_TASK_LEE_LANDED, FORM, vl, direct);
+    if (__any(vt)) OUZ_RUN_ENV(OUZ_TASK_TRACKING, FORM, vt, direct);
+    if (__any(vr)) OUZ_RUN_ENV(OUZ_TASK_FAULT, FORM, vr, direct);
   }
   if constexpr (!MIXT) {   // (a task launch of the split mixed curriculum never reduces statistics: rollout_impl)
     if (sm) reduce_stats(*rst, (uint32_t)first >> 6, (uint32_t)((CLS ? a.n_slots : a.n) + 63) >> 6, ls);
   }
 }
+#undef OUZ_RUN_CHUNK
+#undef OUZ_CHUNK_OF_TILE
+#undef OUZ_RUN_ENV
 
 // VecTask.step: one step, outputs into the env buffers.  Its arguments are StepArgs + one StepCtx
 // (~390 B): the host copies the argument block on every launch (≈0.6 us more host time per launch
 // for a 1.1 KB block, scripts/exp/launch_cost.hip), and at 4096 envs that host time is the bound.
-template <int TASK, bool CLS = false, bool NTL = false, bool QUAD = false, bool MIXT = false>
+constexpr unsigned form_bit(bool flag, unsigned bit) { return flag ? bit : 0u; }
+template <int TASK, bool CLS = false, bool NTL = false, bool QLN = false, bool MIXT = false>
 __global__ void __launch_bounds__(kMaxBlock) quad_step_kernel(StepArgs a, StepCtx c) {
   prefetch_kernargs<(int)(sizeof(StepArgs) + sizeof(StepCtx) + 8)>();
   const OutPtrs env_out[2] = {OutPtrs{a.obs, a.rew, a.reset, a.timeouts}, OutPtrs{a.obs, a.rew, a.reset, a.timeouts}};
-  step_body<TASK, false, false, CLS, NTL, QUAD, false, false, MIXT>(a, &c, 1, env_out, 0);
+  step_body<TASK, form_bit(CLS, F_CLS) | form_bit(NTL, F_NTL) | form_bit(QLN, F_QLN) | form_bit(MIXT, F_MIXT)>(a, &c, 1, env_out, 0);
 }
 
 // ouz_pre_physics: pre_physics_step alone, the body wrench to `wrench` [n][6].
-template <int TASK, bool CLS = false, bool QUAD = false>
+template <int TASK, bool CLS = false, bool QLN = false>
 __global__ void __launch_bounds__(kMaxBlock) quad_pre_kernel(StepArgs a, StepCtx c, float* wrench) {
   const OutPtrs env_out[2] = {OutPtrs{a.obs, a.rew, a.reset, a.timeouts}, OutPtrs{a.obs, a.rew, a.reset, a.timeouts}};
-  step_body<TASK, false, true, CLS, false, QUAD>(a, &c, 1, env_out, 0, nullptr, wrench);
+  step_body<TASK, F_PRE | form_bit(CLS, F_CLS) | form_bit(QLN, F_QLN)>(a, &c, 1, env_out, 0, nullptr, wrench);
 }
 
 // ouz_rollout: K <= kMaxRolloutChunk steps in one launch, env state kept in registers.  SPW: the split-wave
@@ -915,12 +863,13 @@ __global__ void __launch_bounds__(kMaxBlock) quad_pre_kernel(StepArgs a, StepCtx
 // the rollout runs 10-12 % faster per step at 4 M envs (QuadTracking 410 -> 359 us, QuadMixed 380 -> 344:
 // profiles/r04/wide_rollout_ab.txt).
 // PLAIN: the plain-config form (plain_config; launch_task picks it per launch).
-template <int TASK, bool CLS = false, bool QUAD = false, bool SPW = false, bool OWV = false, int WPE = 1,
+template <int TASK, bool CLS = false, bool QLN = false, bool SPW = false, bool OWV = false, int WPE = 1,
           bool MIXT = false, bool PLAIN = false>
 __global__ void __launch_bounds__(kMaxBlock) __attribute__((amdgpu_waves_per_eu(WPE)))
 quad_rollout_kernel(StepArgs a, RolloutArgs r) {
   prefetch_kernargs<(int)(sizeof(StepArgs) + sizeof(RolloutArgs) + 8)>();
-  step_body<TASK, true, false, CLS, false, QUAD, SPW, OWV, MIXT, PLAIN>(a, r.ctx, r.K, r.outs, r.out_stride, &r.stats);
+  step_body<TASK, F_MULTI | form_bit(CLS, F_CLS) | form_bit(QLN, F_QLN) | form_bit(SPW, F_SPW) | form_bit(OWV, F_OWV) |
+                      form_bit(MIXT, F_MIXT) | form_bit(PLAIN, F_PLAIN)>(a, r.ctx, r.K, r.outs, r.out_stride, &r.stats);
 }
 #ifndef OUZ_EST_ROLLOUT_WPE
 #define OUZ_EST_ROLLOUT_WPE 2   // (A/B builds: -DOUZ_EST_ROLLOUT_WPE=3)
@@ -938,7 +887,7 @@ __host__ __device__ constexpr int rollout_wpe(int task, int n) {
 // 80 registers more: a second copy would cost the occupancy this buys).
 constexpr size_t kCtxArgOffset = (sizeof(StepArgs) + alignof(StepCtx) - 1) / alignof(StepCtx) * alignof(StepCtx);
 
-template <int CTRL, int TGT, bool NTL>
+template <int CTRL, int TGT, unsigned FORM>
 __device__ __forceinline__ void pipe_envs(const StepArgs& a, const StepCtx& c, const OutPtrs& o, float* wave_lds,
                                           int t, int tiles, int task) {
   const TaskParams& tp = a.tp[tp_slot(task)];
@@ -947,7 +896,7 @@ __device__ __forceinline__ void pipe_envs(const StepArgs& a, const StepCtx& c, c
   bool valid = i < a.n;
   EnvRegs<CTRL, TGT> S;
   S.T = tile_of(a, i);
-  if (valid) env_load<CTRL, TGT, false, NTL>(a, i, tp, S, c.actions);
+  if (valid) env_load<CTRL, TGT, load_form(FORM)>(a, i, tp, S, c.actions);
   for (;;) {
     // The argument blocks are re-read through laundered pointers every tile: otherwise the compiler
     // hoists the wave-uniform float arithmetic on them (VALU results, held in VGPRs) out of the loop,
@@ -965,16 +914,16 @@ __device__ __forceinline__ void pipe_envs(const StepArgs& a, const StepCtx& c, c
     const bool vn = more && in < A.n;
     EnvRegs<CTRL, TGT> N;
     N.T = tile_of(A, in);
-    if (vn) env_load<CTRL, TGT, false, NTL>(A, in, TP, N, C.actions);
+    if (vn) env_load<CTRL, TGT, load_form(FORM)>(A, in, TP, N, C.actions);
     float ob[OUZ_NUM_OBS];
     float rew = 0.0f;
     bool rs = false, to = false;
     const bool did_reset = valid && S.rst;
     const bool flags_clear = valid && S.flags_clear;
-    if (valid) env_core<CTRL, TGT>(A, C, i, A.env_offset + (uint32_t)i, task, S, ob, rew, rs, to);
+    if (valid) env_core<CTRL, TGT, core_form(FORM)>(A, C, i, A.env_offset + (uint32_t)i, task, S, ob, rew, rs, to);
     trace_count(A, C.step, did_reset, i, i);
     emit(o, wave_lds, i, A.n, valid, ob, rew, rs, to, false, flags_clear);
-    if (valid) env_store<CTRL, TGT>(A, i, TP, S);
+    if (valid) env_store<CTRL, TGT, store_form(FORM)>(A, i, TP, S);
     if (!more) break;
     S = N;
     t = tn;
@@ -1018,8 +967,8 @@ __global__ void __launch_bounds__(kMaxBlock) OUZ_PIPE_ATTR quad_step_pipe_kernel
   const int t = (int)__builtin_amdgcn_readfirstlane(blockIdx.x * (kMaxBlock / 64) + (threadIdx.x >> 6));
   const int tiles = (a.n + 63) >> 6;
   if (t >= tiles) return;
-  if constexpr (TASK == OUZ_TASK_LANDING) pipe_envs<CTRL_RL, TGT_TRAJ, NTL>(a, c, o, wave_lds, t, tiles, TASK);
-  else if constexpr (pipe_task(TASK)) pipe_envs<CTRL_RL, TGT_GOAL, NTL>(a, c, o, wave_lds, t, tiles, TASK);
+  if constexpr (pipe_task(TASK))
+    pipe_envs<task_ctrl(TASK), task_tgt(TASK), form_bit(NTL, F_NTL)>(a, c, o, wave_lds, t, tiles, TASK);
 }
 
 // Creation-time state (VecTask.allocate_buffers vec_task.py:254-277 + task __init__).
@@ -1355,6 +1304,26 @@ int hip_check(hipError_t e, const char* what) {
 inline int grid_for(int n, int block) { return (n + block - 1) / block; }
 inline int block_for(int n) { return step_block_for(n); }   // the step kernel assumes this rule
 
+// One adapter per __global__ kernel: the only place that spells its positional list (the profiles match on it).
+template <int T, unsigned FORM>
+void launch_step(dim3 g, dim3 b, hipStream_t s, const StepArgs& a, const StepCtx& c) {
+  hipLaunchKernelGGL((quad_step_kernel<T, has(FORM, F_CLS), has(FORM, F_NTL), has(FORM, F_QLN), has(FORM, F_MIXT)>), g, b,
+                     0, s, a, c);
+}
+template <int T, unsigned FORM>
+void launch_pipe(dim3 g, dim3 b, hipStream_t s, const StepArgs& a, const StepCtx& c) {
+  hipLaunchKernelGGL((quad_step_pipe_kernel<T, has(FORM, F_NTL)>), g, b, 0, s, a, c);
+}
+template <int T, unsigned FORM>
+void launch_pre(dim3 g, dim3 b, hipStream_t s, const StepArgs& a, const StepCtx& c, float* wrench) {
+  hipLaunchKernelGGL((quad_pre_kernel<T, has(FORM, F_CLS), has(FORM, F_QLN)>), g, b, 0, s, a, c, wrench);
+}
+template <int T, unsigned FORM, int WPE = 1>
+void launch_rollout(dim3 g, dim3 b, hipStream_t s, const StepArgs& a, const RolloutArgs& r) {
+  hipLaunchKernelGGL((quad_rollout_kernel<T, has(FORM, F_CLS), has(FORM, F_QLN), has(FORM, F_SPW), has(FORM, F_OWV), WPE,
+                                          has(FORM, F_MIXT), has(FORM, F_PLAIN)>), g, b, 0, s, a, r);
+}
+
 #define OUZ_LAUNCH_CHECK(what)                                         \
   do {                                                                 \
     hipError_t _e = hipGetLastError();                                 \
@@ -1632,49 +1601,68 @@ static void launch_task(bool single, const StepArgs& a, const RolloutArgs& r, di
   if constexpr (pipe_task(T)) {
     if (single && a.pipe_stride) {
       const dim3 pg(a.pipe_stride / (kMaxBlock / 64)), pb(kMaxBlock);
-      if (a.nt_loads) hipLaunchKernelGGL((quad_step_pipe_kernel<T, true>), pg, pb, 0, s, a, r.ctx[0]);
-      else hipLaunchKernelGGL((quad_step_pipe_kernel<T, false>), pg, pb, 0, s, a, r.ctx[0]);
+      if (a.nt_loads) launch_pipe<T, F_NTL>(pg, pb, s, a, r.ctx[0]);
+      else launch_pipe<T, F_NONE>(pg, pb, s, a, r.ctx[0]);
       return;
     }
   }
   if constexpr (class_layout_task(T)) {
     if (a.cls && a.quad) {   // the quad-lane grid: four 64-lane blocks per 64-slot tile (step_body)
       const dim3 g4(g.x * 4);
-      if (single) hipLaunchKernelGGL((quad_step_kernel<T, true, false, true>), g4, b, 0, s, a, r.ctx[0]);
-      else hipLaunchKernelGGL((quad_rollout_kernel<T, true, true>), g4, b, 0, s, a, r);
+      if (single) launch_step<T, F_CLS | F_QLN>(g4, b, s, a, r.ctx[0]);
+      else launch_rollout<T, F_CLS | F_QLN>(g4, b, s, a, r);
       return;
     }
     if (a.cls && !single && (a.split || a.outw)) {   // multi-wave rollouts: one workgroup per 64-slot tile
-      if (a.split && a.outw) hipLaunchKernelGGL((quad_rollout_kernel<T, true, false, true, true>), g, dim3(192), 0, s, a, r);
-      else if (a.split) hipLaunchKernelGGL((quad_rollout_kernel<T, true, false, true, false>), g, dim3(128), 0, s, a, r);
-      else hipLaunchKernelGGL((quad_rollout_kernel<T, true, false, false, true>), g, dim3(128), 0, s, a, r);
+      if (a.split && a.outw) launch_rollout<T, F_CLS | F_SPW | F_OWV>(g, dim3(192), s, a, r);
+      else if (a.split) launch_rollout<T, F_CLS | F_SPW>(g, dim3(128), s, a, r);
+      else launch_rollout<T, F_CLS | F_OWV>(g, dim3(128), s, a, r);
       return;
     }
     if (a.cls) {
-      if (single) hipLaunchKernelGGL((quad_step_kernel<T, true>), g, b, 0, s, a, r.ctx[0]);
-      else if (rollout_wpe(T, a.n) > 1)
-        hipLaunchKernelGGL((quad_rollout_kernel<T, true, false, false, false, OUZ_EST_ROLLOUT_WPE>), g, b, 0, s, a, r);
-      else hipLaunchKernelGGL((quad_rollout_kernel<T, true>), g, b, 0, s, a, r);
+      if (single) launch_step<T, F_CLS>(g, b, s, a, r.ctx[0]);
+      else if (rollout_wpe(T, a.n) > 1) launch_rollout<T, F_CLS, OUZ_EST_ROLLOUT_WPE>(g, b, s, a, r);
+      else launch_rollout<T, F_CLS>(g, b, s, a, r);
       return;
     }
   }
-  if (single && a.nt_loads) hipLaunchKernelGGL((quad_step_kernel<T, false, true>), g, b, 0, s, a, r.ctx[0]);
-  else if (single) hipLaunchKernelGGL((quad_step_kernel<T, false, false>), g, b, 0, s, a, r.ctx[0]);
+  if (single && a.nt_loads) launch_step<T, F_NTL>(g, b, s, a, r.ctx[0]);
+  else if (single) launch_step<T, F_NONE>(g, b, s, a, r.ctx[0]);
   else if (T != OUZ_TASK_MIXED && a.outw) {
     // the plain form where this launch's configuration allows it: the options it leaves out can be set between launches
     if constexpr (plain_task(T)) {
       if (a.plain && plain_config(a, T)) {
-        hipLaunchKernelGGL((quad_rollout_kernel<T, false, false, false, true, 1, false, true>), g, dim3(128), 0, s, a, r);
+        launch_rollout<T, F_OWV | F_PLAIN>(g, dim3(128), s, a, r);
         return;
       }
     }
-    hipLaunchKernelGGL((quad_rollout_kernel<T, false, false, false, T != OUZ_TASK_MIXED>), g, dim3(128), 0, s, a, r);
+    launch_rollout<T, (T != OUZ_TASK_MIXED ? F_OWV : F_NONE)>(g, dim3(128), s, a, r);
   }
   else if (class_layout_task(T) && rollout_wpe(T, a.n) > 1)
-    hipLaunchKernelGGL((quad_rollout_kernel<T, false, false, false, false, (class_layout_task(T) ? OUZ_EST_ROLLOUT_WPE : 1)>), g, b,
-                       0, s, a, r);
-  else hipLaunchKernelGGL((quad_rollout_kernel<T, false>), g, b, 0, s, a, r);
+    launch_rollout<T, F_NONE, (class_layout_task(T) ? OUZ_EST_ROLLOUT_WPE : 1)>(g, b, s, a, r);
+  else launch_rollout<T, F_NONE>(g, b, s, a, r);
 }
+
+extern "C++" template <int T>   // ouz_pre_physics' kernel of one task
+static void launch_pre_task(const StepArgs& a, const StepCtx& c, float* wrench, dim3 g, dim3 b, hipStream_t s) {
+  if constexpr (class_layout_task(T)) {
+    if (a.cls && a.quad) return launch_pre<T, F_CLS | F_QLN>(dim3(g.x * 4), b, s, a, c, wrench);   // the quad-lane grid
+    if (a.cls) return launch_pre<T, F_CLS>(g, b, s, a, c, wrench);
+  }
+  launch_pre<T, F_NONE>(g, b, s, a, c, wrench);
+}
+
+// FN<T> ARGS with the configured task as the constant T
+#define OUZ_TASK_SWITCH(task, FN, ARGS)                                            \
+  switch (task) {                                                                  \
+    case OUZ_TASK_OUZELUM: FN<OUZ_TASK_OUZELUM> ARGS; break;                       \
+    case OUZ_TASK_LEE_LANDED: FN<OUZ_TASK_LEE_LANDED> ARGS; break;                 \
+    case OUZ_TASK_EKF_LEE_LANDED: FN<OUZ_TASK_EKF_LEE_LANDED> ARGS; break;         \
+    case OUZ_TASK_TRACKING: FN<OUZ_TASK_TRACKING> ARGS; break;                     \
+    case OUZ_TASK_FAULT: FN<OUZ_TASK_FAULT> ARGS; break;                           \
+    case OUZ_TASK_LANDING: FN<OUZ_TASK_LANDING> ARGS; break;                       \
+    default: FN<OUZ_TASK_MIXED> ARGS; break;                                       \
+  }
 
 // Waves of the launch of task T over the mixed curriculum's shard (mixed_task_tile): 21 per chunk of that task
 // that touches the shard (the first and last chunk may be partial: their waves past the shard exit at once).
@@ -1692,11 +1680,10 @@ static void launch_mixed_task(bool single, const StepArgs& a, const RolloutArgs&
   const int waves = mixed_task_waves(a, T), wpb = (int)b.x / 64;
   if (waves == 0) return;
   const dim3 g((waves + wpb - 1) / wpb);
-  if (single && a.nt_loads) hipLaunchKernelGGL((quad_step_kernel<T, false, true, false, true>), g, b, 0, s, a, r.ctx[0]);
-  else if (single) hipLaunchKernelGGL((quad_step_kernel<T, false, false, false, true>), g, b, 0, s, a, r.ctx[0]);
-  else if (T == OUZ_TASK_TRACKING)
-    hipLaunchKernelGGL((quad_rollout_kernel<T, false, false, false, false, OUZ_EST_ROLLOUT_WPE, true>), g, b, 0, s, a, r);
-  else hipLaunchKernelGGL((quad_rollout_kernel<T, false, false, false, false, 1, true>), g, b, 0, s, a, r);
+  if (single && a.nt_loads) launch_step<T, F_MIXT | F_NTL>(g, b, s, a, r.ctx[0]);
+  else if (single) launch_step<T, F_MIXT>(g, b, s, a, r.ctx[0]);
+  else if (T == OUZ_TASK_TRACKING) launch_rollout<T, F_MIXT, OUZ_EST_ROLLOUT_WPE>(g, b, s, a, r);
+  else launch_rollout<T, F_MIXT>(g, b, s, a, r);
 }
 
 static uint32_t cached_flicker_mask(ouz_env* env, int64_t step) {
@@ -1724,6 +1711,61 @@ static void prefill_flicker_masks(ouz_env* env, int64_t from, int count) {
     env->mask[env->mask_n++] = flicker_mask(env->args, env->cfg.task, (uint32_t)st);
 }
 
+// Row g of rollout storage ([n_steps][N][...] buffers, N envs per row).
+static OutPtrs storage_row(const OutPtrs& st, size_t n, size_t g) {
+  return OutPtrs{st.obs + g * n * OUZ_NUM_OBS, st.rew + g * n, st.reset + g * n, st.timeouts + g * n};
+}
+
+// A launch of K steps from env->step on: ring batch (ring_pos + k) % ring_len, row k of `storage` (null: env buffers).
+static void fill_rollout_args(ouz_env* env, RolloutArgs& r, int32_t K, const OutPtrs* storage, const float* ring,
+                              int32_t ring_len, int64_t ring_pos) {
+  const size_t n = (size_t)env->cfg.num_envs;
+  std::memset(&r, 0, sizeof(r));
+  r.K = K;
+  const OutPtrs envout{env->buf.obs, env->buf.rew, env->buf.reset, env->buf.timeouts};
+  r.outs[0] = storage ? *storage : envout;
+  r.outs[1] = envout;
+  r.out_stride = storage ? (uint64_t)n : 0;
+  for (int k = 0; k < K; ++k) {
+    r.ctx[k].step = (uint32_t)(env->step + k);
+    r.ctx[k].flick_mask = cached_flicker_mask(env, env->step + k);
+    r.ctx[k].actions = ring ? ring + (size_t)((ring_pos + k) % ring_len) * n * OUZ_NUM_ACT : nullptr;
+  }
+}
+
+// Step g of a streamed rollout of n_steps: it reads the flags of row g - 1 and writes row g; the last step (and every
+// step without storage) writes the env buffers, which copy_last_row then copies into the last row.
+static StepArgs streamed_step_args(const ouz_env* env, const OutPtrs* storage, int32_t g, int32_t n_steps) {
+  StepArgs a = env->args;
+  const size_t n = (size_t)env->cfg.num_envs;
+  if (storage && g > 0) {
+    const OutPtrs prev = storage_row(*storage, n, (size_t)g - 1);
+    a.rst_in = prev.reset;
+    a.to_in = prev.timeouts;
+  }
+  if (storage && g + 1 < n_steps) {
+    const OutPtrs row = storage_row(*storage, n, (size_t)g);
+    a.obs = row.obs;
+    a.rew = row.rew;
+    a.reset = row.reset;
+    a.timeouts = row.timeouts;
+  }
+  return a;
+}
+static int copy_last_row(const ouz_env* env, const OutPtrs& storage, int32_t n_steps, hipStream_t s) {
+  const size_t n = (size_t)env->cfg.num_envs;
+  const OutPtrs last = storage_row(storage, n, (size_t)n_steps - 1);
+  int rc = hip_check(hipMemcpyAsync(last.obs, env->buf.obs, n * OUZ_NUM_OBS * sizeof(float), hipMemcpyDeviceToDevice, s),
+                     "hipMemcpyAsync(rollout obs)");
+  if (!rc) rc = hip_check(hipMemcpyAsync(last.rew, env->buf.rew, n * sizeof(float), hipMemcpyDeviceToDevice, s),
+                          "hipMemcpyAsync(rollout rew)");
+  if (!rc) rc = hip_check(hipMemcpyAsync(last.reset, env->buf.reset, n * sizeof(int64_t), hipMemcpyDeviceToDevice, s),
+                          "hipMemcpyAsync(rollout reset)");
+  if (!rc) rc = hip_check(hipMemcpyAsync(last.timeouts, env->buf.timeouts, n, hipMemcpyDeviceToDevice, s),
+                          "hipMemcpyAsync(rollout timeouts)");
+  return rc;
+}
+
 // Launch K (<= kMaxRolloutChunk) consecutive steps as ONE kernel.  K = 1 is VecTask.step.
 // ring: action batches [ring_len][N][4] (step k uses batch (ring_pos + k) % ring_len) or null.
 // storage: per-step outputs for these K steps ([K][N][...]) or null (outputs go to the env buffers).
@@ -1733,48 +1775,25 @@ static int launch_steps(ouz_env* env, const float* ring, int32_t ring_len, int64
   const StepArgs& a = args ? *args : env->args;
   const int n = env->cfg.num_envs, blk = block_for(n);
   RolloutArgs r;
-  std::memset(&r, 0, sizeof(r));
-  r.K = K;
+  fill_rollout_args(env, r, K, storage, ring, ring_len, ring_pos);
   if (stats_mode) r.stats = RolloutStats{stats_out, env->wave_partials, env->wave_ticket, stats_mode};
-  const OutPtrs envout{env->buf.obs, env->buf.rew, env->buf.reset, env->buf.timeouts};
-  r.outs[0] = storage ? *storage : envout;
-  r.outs[1] = envout;
-  r.out_stride = storage ? (uint64_t)n : 0;
-  for (int k = 0; k < K; ++k) {
-    const uint32_t step = (uint32_t)(env->step + k);
-    r.ctx[k].step = step;
-    r.ctx[k].flick_mask = cached_flicker_mask(env, env->step + k);
-    r.ctx[k].actions = ring ? ring + (size_t)((ring_pos + k) % ring_len) * n * OUZ_NUM_ACT : nullptr;
-  }
   dim3 g(grid_for(a.n_slots, blk)), b(blk);   // one lane per state slot
   if (a.xcd_pack) {   // whole class blocks per XCD (xcd_tile)
     const int per_xcd = (a.n_slots / kClassBlock + 7) / 8 * kTrigClasses;
     g = dim3(8 * ((per_xcd + blk / 64 - 1) / (blk / 64)));
   }
   const bool single = K == 1 && !storage && !stats_mode;
-  if (env->cfg.task == OUZ_TASK_MIXED && a.mix_split && single) {
+  const bool per_task = env->cfg.task == OUZ_TASK_MIXED && a.mix_split && single;
+  if (per_task) {
     // VecTask.step as one launch per task over its chunks' tiles (mixed_task_tile).  A fused rollout keeps the
     // one-launch kernel unless OUZ_MIXED_SPLIT_ROLLOUT=1 (rollout_impl -> mixed_rollout)
     launch_mixed_task<OUZ_TASK_LEE_LANDED>(single, a, r, b, s);
     launch_mixed_task<OUZ_TASK_TRACKING>(single, a, r, b, s);
     launch_mixed_task<OUZ_TASK_FAULT>(single, a, r, b, s);
-    OUZ_LAUNCH_CHECK("quad_step_kernel (mixed, per task)");
-    env->step += K;
-    prefill_flicker_masks(env, env->step, kMaxRolloutChunk);
-    return OUZ_OK;
+  } else {
+    OUZ_TASK_SWITCH(env->cfg.task, launch_task, (single, a, r, g, b, s))
   }
-#define OUZ_LAUNCH_TASK(T) launch_task<T>(single, a, r, g, b, s)
-  switch (env->cfg.task) {
-    case OUZ_TASK_OUZELUM: OUZ_LAUNCH_TASK(OUZ_TASK_OUZELUM); break;
-    case OUZ_TASK_LEE_LANDED: OUZ_LAUNCH_TASK(OUZ_TASK_LEE_LANDED); break;
-    case OUZ_TASK_EKF_LEE_LANDED: OUZ_LAUNCH_TASK(OUZ_TASK_EKF_LEE_LANDED); break;
-    case OUZ_TASK_TRACKING: OUZ_LAUNCH_TASK(OUZ_TASK_TRACKING); break;
-    case OUZ_TASK_FAULT: OUZ_LAUNCH_TASK(OUZ_TASK_FAULT); break;
-    case OUZ_TASK_LANDING: OUZ_LAUNCH_TASK(OUZ_TASK_LANDING); break;
-    default: OUZ_LAUNCH_TASK(OUZ_TASK_MIXED); break;
-  }
-#undef OUZ_LAUNCH_TASK
-  OUZ_LAUNCH_CHECK("quad_step_kernel");
+  OUZ_LAUNCH_CHECK(per_task ? "quad_step_kernel (mixed, per task)" : "quad_step_kernel");
   env->step += K;
   prefill_flicker_masks(env, env->step, kMaxRolloutChunk);   // the next launch's coins, while this one runs
   return OUZ_OK;
@@ -1814,42 +1833,18 @@ int ouz_step_n(ouz_env* env, const float* ring, int32_t ring_len, int32_t n_step
 // the form those tasks take at this size on their own.  Every env runs the same per-env code as in the one-launch
 // kernel (equal within float tolerance, as the fused and streamed forms are).  The episode statistics are one
 // ouz_episode_stats launch after the steps, as for a streamed rollout.
-static int mixed_rollout(ouz_env* env, const float* ring, int32_t ring_len, int32_t n_steps, float* obs_out,
-                         float* rew_out, int64_t* reset_out, uint8_t* timeouts_out, double* stats_out, int stats_mode,
-                         hipStream_t s) {
-  const bool store = obs_out != nullptr;
+static int mixed_rollout(ouz_env* env, const float* ring, int32_t ring_len, int32_t n_steps, const OutPtrs* storage,
+                         double* stats_out, int stats_mode, hipStream_t s) {
   const size_t n = (size_t)env->cfg.num_envs;
   const dim3 b(block_for((int)n));
-  const OutPtrs envout{env->buf.obs, env->buf.rew, env->buf.reset, env->buf.timeouts};
   for (int32_t k0 = 0; k0 < n_steps; k0 += kMaxRolloutChunk) {
     const int32_t K = (n_steps - k0) < kMaxRolloutChunk ? (n_steps - k0) : kMaxRolloutChunk;
-    const int64_t base = env->step;
+    const OutPtrs rows = storage ? storage_row(*storage, n, (size_t)k0) : OutPtrs{};
     RolloutArgs r;
-    std::memset(&r, 0, sizeof(r));
-    r.K = K;
-    for (int k = 0; k < K; ++k) {
-      r.ctx[k].step = (uint32_t)(base + k);
-      r.ctx[k].flick_mask = cached_flicker_mask(env, base + k);
-      r.ctx[k].actions = ring ? ring + (size_t)((k0 + k) % ring_len) * n * OUZ_NUM_ACT : nullptr;
-    }
-    r.outs[0] = store ? OutPtrs{obs_out + (size_t)k0 * n * OUZ_NUM_OBS, rew_out + (size_t)k0 * n,
-                                reset_out + (size_t)k0 * n, timeouts_out + (size_t)k0 * n} : envout;
-    r.outs[1] = envout;
-    r.out_stride = store ? (uint64_t)n : 0;
+    fill_rollout_args(env, r, K, storage ? &rows : nullptr, ring, ring_len, k0);
     launch_mixed_task<OUZ_TASK_TRACKING>(false, env->args, r, b, s);
     for (int32_t k = 0; k < K; ++k) {   // the streamed tasks, step by step (rollout_impl's streamed path)
-      const int32_t g = k0 + k;
-      StepArgs a = env->args;
-      if (store && g > 0) {
-        a.rst_in = reset_out + (size_t)(g - 1) * n;
-        a.to_in = timeouts_out + (size_t)(g - 1) * n;
-      }
-      if (store && g + 1 < n_steps) {
-        a.obs = obs_out + (size_t)g * n * OUZ_NUM_OBS;
-        a.rew = rew_out + (size_t)g * n;
-        a.reset = reset_out + (size_t)g * n;
-        a.timeouts = timeouts_out + (size_t)g * n;
-      }
+      const StepArgs a = streamed_step_args(env, storage, k0 + k, n_steps);
       RolloutArgs r1;
       std::memset(&r1, 0, sizeof(r1));
       r1.K = 1;
@@ -1858,20 +1853,11 @@ static int mixed_rollout(ouz_env* env, const float* ring, int32_t ring_len, int3
       launch_mixed_task<OUZ_TASK_FAULT>(true, a, r1, b, s);
     }
     OUZ_LAUNCH_CHECK("quad kernels (mixed rollout, per task)");
-    env->step = base + K;
+    env->step += K;
     prefill_flicker_masks(env, env->step, kMaxRolloutChunk);
   }
-  if (store && n_steps > 0) {   // the streamed tasks' last step wrote the env buffers (the fused one wrote both)
-    const size_t last = (size_t)(n_steps - 1) * n;
-    const ouz_buffers& bf = env->buf;
-    int rc = hip_check(hipMemcpyAsync(obs_out + last * OUZ_NUM_OBS, bf.obs, n * OUZ_NUM_OBS * sizeof(float),
-                                      hipMemcpyDeviceToDevice, s), "hipMemcpyAsync(rollout obs)");
-    if (!rc) rc = hip_check(hipMemcpyAsync(rew_out + last, bf.rew, n * sizeof(float), hipMemcpyDeviceToDevice, s),
-                            "hipMemcpyAsync(rollout rew)");
-    if (!rc) rc = hip_check(hipMemcpyAsync(reset_out + last, bf.reset, n * sizeof(int64_t), hipMemcpyDeviceToDevice, s),
-                            "hipMemcpyAsync(rollout reset)");
-    if (!rc) rc = hip_check(hipMemcpyAsync(timeouts_out + last, bf.timeouts, n, hipMemcpyDeviceToDevice, s),
-                            "hipMemcpyAsync(rollout timeouts)");
+  if (storage && n_steps > 0) {   // the streamed tasks' last step wrote the env buffers (the fused one wrote both)
+    const int rc = copy_last_row(env, *storage, n_steps, s);
     if (rc) return rc;
   }
   return stats_mode ? ouz_episode_stats(env, stats_out, stats_mode == 2 ? 1 : 0, s) : OUZ_OK;
@@ -1886,51 +1872,30 @@ static int rollout_impl(ouz_env* env, const float* ring, int32_t ring_len, int32
   if (store && !(obs_out && rew_out && reset_out && timeouts_out))
     return fail(OUZ_ERR_INVALID, std::string(fn) + ": give all four storage pointers or none");
   const size_t n = (size_t)env->cfg.num_envs;
+  const hipStream_t s = (hipStream_t)stream;
+  const OutPtrs all_rows{obs_out, rew_out, reset_out, timeouts_out};
+  const OutPtrs* storage = store ? &all_rows : nullptr;
   if (env->cfg.task == OUZ_TASK_MIXED && env->args.mix_split && env->mix_split_rollout)
-    return mixed_rollout(env, ring, ring_len, n_steps, obs_out, rew_out, reset_out, timeouts_out, stats_out,
-                         stats_mode, (hipStream_t)stream);
+    return mixed_rollout(env, ring, ring_len, n_steps, storage, stats_out, stats_mode, s);
   if (env->stream_rollout) {
-    // Streamed: step k reads the flags of row k - 1 and writes row k; the last step writes the env buffers,
-    // which are then copied into the last row.  Bitwise K VecTask.step calls (the fused kernel is the same
+    // Streamed (streamed_step_args).  Bitwise K VecTask.step calls (the fused kernel is the same
     // per-env code in another loop, equal within float tolerance: tests/test_gpu_env.py).
-    const hipStream_t s = (hipStream_t)stream;
     for (int32_t k = 0; k < n_steps; ++k) {
-      StepArgs a = env->args;
-      if (store && k > 0) {
-        a.rst_in = reset_out + (size_t)(k - 1) * n;
-        a.to_in = timeouts_out + (size_t)(k - 1) * n;
-      }
-      if (store && k + 1 < n_steps) {
-        a.obs = obs_out + (size_t)k * n * OUZ_NUM_OBS;
-        a.rew = rew_out + (size_t)k * n;
-        a.reset = reset_out + (size_t)k * n;
-        a.timeouts = timeouts_out + (size_t)k * n;
-      }
+      const StepArgs a = streamed_step_args(env, storage, k, n_steps);
       rc = launch_steps(env, ring, ring_len, k, 1, nullptr, s, nullptr, 0, &a);
       if (rc) return rc;
     }
     if (store && n_steps > 0) {
-      const size_t last = (size_t)(n_steps - 1) * n;
-      const ouz_buffers& b = env->buf;
-      rc = hip_check(hipMemcpyAsync(obs_out + last * OUZ_NUM_OBS, b.obs, n * OUZ_NUM_OBS * sizeof(float),
-                                    hipMemcpyDeviceToDevice, s), "hipMemcpyAsync(rollout obs)");
-      if (!rc) rc = hip_check(hipMemcpyAsync(rew_out + last, b.rew, n * sizeof(float), hipMemcpyDeviceToDevice, s),
-                              "hipMemcpyAsync(rollout rew)");
-      if (!rc) rc = hip_check(hipMemcpyAsync(reset_out + last, b.reset, n * sizeof(int64_t), hipMemcpyDeviceToDevice, s),
-                              "hipMemcpyAsync(rollout reset)");
-      if (!rc) rc = hip_check(hipMemcpyAsync(timeouts_out + last, b.timeouts, n, hipMemcpyDeviceToDevice, s),
-                              "hipMemcpyAsync(rollout timeouts)");
+      rc = copy_last_row(env, all_rows, n_steps, s);
       if (rc) return rc;
     }
     return stats_mode ? ouz_episode_stats(env, stats_out, stats_mode == 2 ? 1 : 0, stream) : OUZ_OK;
   }
   for (int32_t k0 = 0; k0 < n_steps; k0 += kMaxRolloutChunk) {
     const int32_t K = (n_steps - k0) < kMaxRolloutChunk ? (n_steps - k0) : kMaxRolloutChunk;
-    OutPtrs st{obs_out + (size_t)k0 * n * OUZ_NUM_OBS, rew_out + (size_t)k0 * n, reset_out + (size_t)k0 * n,
-               timeouts_out + (size_t)k0 * n};
+    const OutPtrs rows = store ? storage_row(all_rows, n, (size_t)k0) : OutPtrs{};
     const bool last = k0 + K >= n_steps;
-    rc = launch_steps(env, ring, ring_len, k0, K, store ? &st : nullptr, (hipStream_t)stream, stats_out,
-                      last ? stats_mode : 0);
+    rc = launch_steps(env, ring, ring_len, k0, K, store ? &rows : nullptr, s, stats_out, last ? stats_mode : 0);
     if (rc) return rc;
   }
   return OUZ_OK;
@@ -1961,29 +1926,8 @@ int ouz_pre_physics(ouz_env* env, const float* actions, float* wrench, void* str
   const int n = env->cfg.num_envs, blk = block_for(n);
   StepCtx c{(uint32_t)env->step, cached_flicker_mask(env, env->step), actions};
   dim3 g(grid_for(a.n_slots, blk)), b(blk);
-  const dim3 g4(g.x * 4);   // the quad-lane grid of the class layout (step_body)
   hipStream_t s = (hipStream_t)stream;
-  switch (env->cfg.task) {
-    case OUZ_TASK_OUZELUM: hipLaunchKernelGGL(quad_pre_kernel<OUZ_TASK_OUZELUM>, g, b, 0, s, a, c, wrench); break;
-    case OUZ_TASK_LEE_LANDED: hipLaunchKernelGGL(quad_pre_kernel<OUZ_TASK_LEE_LANDED>, g, b, 0, s, a, c, wrench); break;
-    case OUZ_TASK_EKF_LEE_LANDED:
-      if (a.cls && a.quad) hipLaunchKernelGGL((quad_pre_kernel<OUZ_TASK_EKF_LEE_LANDED, true, true>), g4, b, 0, s, a, c, wrench);
-      else if (a.cls) hipLaunchKernelGGL((quad_pre_kernel<OUZ_TASK_EKF_LEE_LANDED, true>), g, b, 0, s, a, c, wrench);
-      else hipLaunchKernelGGL((quad_pre_kernel<OUZ_TASK_EKF_LEE_LANDED, false>), g, b, 0, s, a, c, wrench);
-      break;
-    case OUZ_TASK_TRACKING:
-      if (a.cls && a.quad) hipLaunchKernelGGL((quad_pre_kernel<OUZ_TASK_TRACKING, true, true>), g4, b, 0, s, a, c, wrench);
-      else if (a.cls) hipLaunchKernelGGL((quad_pre_kernel<OUZ_TASK_TRACKING, true>), g, b, 0, s, a, c, wrench);
-      else hipLaunchKernelGGL((quad_pre_kernel<OUZ_TASK_TRACKING, false>), g, b, 0, s, a, c, wrench);
-      break;
-    case OUZ_TASK_FAULT: hipLaunchKernelGGL(quad_pre_kernel<OUZ_TASK_FAULT>, g, b, 0, s, a, c, wrench); break;
-    case OUZ_TASK_LANDING: hipLaunchKernelGGL(quad_pre_kernel<OUZ_TASK_LANDING>, g, b, 0, s, a, c, wrench); break;
-    default:
-      if (a.cls && a.quad) hipLaunchKernelGGL((quad_pre_kernel<OUZ_TASK_MIXED, true, true>), g4, b, 0, s, a, c, wrench);
-      else if (a.cls) hipLaunchKernelGGL((quad_pre_kernel<OUZ_TASK_MIXED, true>), g, b, 0, s, a, c, wrench);
-      else hipLaunchKernelGGL((quad_pre_kernel<OUZ_TASK_MIXED, false>), g, b, 0, s, a, c, wrench);
-      break;
-  }
+  OUZ_TASK_SWITCH(env->cfg.task, launch_pre_task, (a, c, wrench, g, b, s))
   OUZ_LAUNCH_CHECK("quad_pre_kernel");
   return OUZ_OK;
 }
