@@ -80,7 +80,7 @@ extern "C" {
                                   with no struct or signature changed: the running normalisation (ouz_moments_batch,
                                   ouz_moments_merge, ouz_normalize_rows, ouz_linear_tanh_small_k_norm), the value
                                   bootstrap (ouz_gae_bootstrap), the bounded atan2 beside the library's
-                                  (ouz_atan2_pair) */
+                                  (ouz_atan2_pair), the packed-pair forms beside the scalar ones (ouz_packed_pair) */
 
 /* error codes */
 #define OUZ_OK 0
@@ -380,6 +380,15 @@ int ouz_lee_control(int32_t mode, const float* state, const float* cmd, float* t
  * arguments of magnitude <= 2^96), and the library atan2f of the same n pairs (y, x), side by side: the two are
  * equal bit for bit under that precondition (tests/test_gpu_oneblock_rollout.py). */
 int ouz_atan2_pair(const float* y, const float* x, float* bounded, float* library, int32_t n, void* stream);
+/* The packed-pair forms of the plain LeeLanded rollout's 3-vector math (quad_math.h) and the scalar forms they restate,
+ * side by side on n rows of OUZ_PACKED_PAIR_IN floats (a[3] b[3] c[3] qa[4] qb[4] s d[3] e[3] wmax fz h yaw_rate): each
+ * output gets OUZ_PACKED_PAIR_OUT floats per row: + - scale mul cross mv mtv (21), quat_to_mat(qa) (9), unit2(a.x, b.x)
+ * (2), euler_sc of the rows a b c (6), quat_mul(qa, qb) (4), the third column of R(qa) (3), qb normalised (4),
+ * lee_attitude_loop (3), lee_position_R (thrust, torque: 4), integrate_thrust_body (p q v w R: 22).  The two are
+ * equal bit for bit (tests/test_gpu_packed_step.py). */
+#define OUZ_PACKED_PAIR_IN 28
+#define OUZ_PACKED_PAIR_OUT 78
+int ouz_packed_pair(const float* in, float* scalar, float* packed, int32_t n, void* stream);
 int ouz_ekf_update(const float* q_wxyz, const float* P10, const float* gyr, const float* ang_wxyz, float dt,
                    float* q_out, float* P10_out, int32_t n, void* stream);
 int ouz_pv_predict(float* x9, float* P45, const float* acc, const float* q_wxyz, float dt, int32_t n,

@@ -151,6 +151,7 @@ SIGNATURES = {
     "ouz_set_step": (_I, [_P, _I64]),
     "ouz_lee_control": (_I, [_I, _P, _P, _P, _P, _I, _P]),
     "ouz_atan2_pair": (_I, [_P, _P, _P, _P, _I, _P]),
+    "ouz_packed_pair": (_I, [_P, _P, _P, _I, _P]),
     "ouz_ekf_update": (_I, [_P, _P, _P, _P, _F, _P, _P, _I, _P]),
     "ouz_pv_predict": (_I, [_P, _P, _P, _P, _F, _I, _P]),
     "ouz_pv_correct": (_I, [_P, _P, _P, _I, _F, _P, _I, _P]),

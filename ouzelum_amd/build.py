@@ -39,7 +39,10 @@ FLAGS = ["-O3", "-std=c++17", "-shared", "-fPIC", f"--offload-arch={ARCH}", "-Wn
          # to stay bitwise equal; with "on" they are equal by construction.
          "-ffp-contract=on",
          # no SLP packing of f32 pairs into v_pk_*: on this per-lane scalar code it only adds register-pair
-         # moves (v_mov -60 %, -5..7 % instructions per step phase) and ~40 VGPRs in the estimator kernels
+         # moves (v_mov -60 %, -5..7 % instructions per step phase) and ~40 VGPRs in the estimator kernels: it picks
+         # pairs expression by expression, with no layout.  Where packing pays it is written by hand with one layout
+         # (quad_math.h P3 / PQ / PR: the plain LeeLanded rollout's state wave, 468 -> 411 instructions per step,
+         # +7 % env-steps/s; docs/HISTORY.md round 20), and this flag keeps the rest scalar.
          "-fno-slp-vectorize",
          # f32 denormals flush to zero: rcp / rsq / sqrt become single instructions instead of 5-6 with
          # range scaling (-7..10 % instructions in the controller / integrator phases).  State, RNG uniforms

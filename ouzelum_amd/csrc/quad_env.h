@@ -94,6 +94,20 @@ constexpr bool form_carry(unsigned form, int ctrl) { return OUZ_CARRY_R != 0 && 
 // LeeLanded gained with them at 4096 and at 8192 envs, QuadFault lost 4.5 % at both (docs/HISTORY.md round 18).
 constexpr bool form_rare(unsigned form, int ctrl) { return has(form, F_PLAIN) && ctrl == CTRL_LEE_TRUE; }
 constexpr bool form_write_through(unsigned form, int task) { return has(form, F_PLAIN) && task == OUZ_TASK_LEE_LANDED; }
+// The plain LeeLanded rollout's state wave alone: its controller and integrator in the packed-pair forms of
+// quad_math.h, bit for bit the scalar forms' values (docs/HISTORY.md round 20).  Its carried R(q) is then a PR.
+#ifdef OUZ_HOST
+constexpr bool form_packed(unsigned, int) { return false; }
+template <unsigned FORM, int CTRL> using CarryR = M3;
+#else
+#ifndef OUZ_PACKED
+#define OUZ_PACKED 1   // 0: an A/B build with the scalar forms everywhere
+#endif
+constexpr bool form_packed(unsigned form, int ctrl) { return OUZ_PACKED != 0 && form_carry(form, ctrl) && form_rare(form, ctrl); }
+template <unsigned FORM, int CTRL> using CarryR = std::conditional_t<form_packed(FORM, CTRL), PR, M3>;
+OUZ_DEV void carry_set(PR& R, Q4 q) { R = quat_to_mat(pq(q)); }
+#endif
+OUZ_DEV void carry_set(M3& R, Q4 q) { R = quat_to_mat(q); }
 // The part of a form that each leaf reads: callers instantiate it on that part alone (it asserts so), and forms that
 // differ elsewhere share one instantiation.  F_QLN in load_form / store_form: the PV covariance is not in registers.
 constexpr unsigned actions_form(unsigned f) { return f & F_CLS; }
@@ -810,7 +824,8 @@ template <int CTRL, int TGT, unsigned FORM = 0u>
 OUZ_DEV void env_core(const StepArgs& a, const StepCtx& sc, int i, uint32_t gid, int task,
                                          EnvRegs<CTRL, TGT>& S, float* ob, float& rew, bool& rs, bool& timeout,
                                          float* wrench = nullptr, const PvQl* ql = nullptr,
-                                         const SplitLane* spl = nullptr, V3* post_target = nullptr, M3* Rc = nullptr) {
+                                         const SplitLane* spl = nullptr, V3* post_target = nullptr,
+                                         CarryR<FORM, CTRL>* Rc = nullptr) {
   constexpr bool PRE = has(FORM, F_PRE), QLN = has(FORM, F_QLN), SPW = has(FORM, F_SPW), OWV = has(FORM, F_OWV),
                  PLAIN = has(FORM, F_PLAIN), CARRY = form_carry(FORM, CTRL);
   static_assert(FORM == core_form(FORM), "instantiate on core_form(FORM)");
@@ -844,7 +859,7 @@ OUZ_DEV void env_core(const StepArgs& a, const StepCtx& sc, int i, uint32_t gid,
     U4 r = draw(a.seed, gid, sc.step, RNG_RESET_POS);
     S.p = v3(uniform_f32(r.x, -1.5f, 1.5f), uniform_f32(r.y, -1.5f, 1.5f), __fadd_rn(1.0f, uniform_f32(r.z, -0.2f, 1.5f)));
     S.q = Q4{0.0f, 0.0f, 0.0f, 1.0f};
-    if constexpr (CARRY) *Rc = quat_to_mat(S.q);
+    if constexpr (CARRY) carry_set(*Rc, S.q);
     S.v = v3(0.0f, 0.0f, 0.0f);
     S.w = v3(0.0f, 0.0f, 0.0f);
     S.progress = 0;
@@ -888,6 +903,9 @@ OUZ_DEV void env_core(const StepArgs& a, const StepCtx& sc, int i, uint32_t gid,
   platform_prefetch<CTRL, TGT>(a, S);
   V3 f_b = v3(0.0f, 0.0f, 0.0f), tau_b = v3(0.0f, 0.0f, 0.0f);
   M3 R0;   // quat_to_mat of the (post-reset) state quaternion: shared by the controller and the integrator
+#ifndef OUZ_HOST
+  P3 tau_p{};   // form_packed: the torque, from the controller to the integrator
+#endif
 
   if constexpr (CTRL == CTRL_RL) {
     // ---- RL per-rotor thrust model (ouzelum.py:218-251) ----
@@ -930,12 +948,33 @@ OUZ_DEV void env_core(const StepArgs& a, const StepCtx& sc, int i, uint32_t gid,
     float T;
     V3 tau;
     const V3 cmd = v3(0.0f, 0.0f, 1.0f);
-    if constexpr (CARRY) R0 = *Rc;
-    else R0 = quat_to_mat(S.q);
-    lee_position_R<true>(R0, S.p, S.v, S.w, cmd, 0.0f, default_gains(), T, tau);
+    if constexpr (form_packed(FORM, CTRL)) {
+#ifndef OUZ_HOST
+      lee_position_R(*Rc, p3(S.p), p3(S.v), p3(S.w), cmd.z, gains_p(default_gains()), T, tau_p);
+#endif
+    } else {
+      if constexpr (CARRY) R0 = *Rc;
+      else R0 = quat_to_mat(S.q);
+      lee_position_R<true>(R0, S.p, S.v, S.w, cmd, 0.0f, default_gains(), T, tau);
+    }
     float fz = 2.0f * kGravity * T;
     V3 dd = cmd - S.p;
-    if constexpr (PLAIN) {
+    if constexpr (form_packed(FORM, CTRL)) {
+#ifndef OUZ_HOST
+      // the PLAIN selects below on the packed torque, every arm a local value: each is a select from the start
+      const bool landed = sqrtf(dot(dd, dd)) < tp.land_radius;
+      const int32_t flag = S.land_flag;
+      const uint32_t dirty = S.dirty, dirty_landed = dirty | D_LAND;
+      S.land_flag = landed ? 1 : flag;
+      S.dirty = landed ? dirty_landed : dirty;
+      const float fz_on = fz;
+      fz = landed ? 0.0f : fz_on;
+      const F2 zero{0.0f, 0.0f}, txy = tau_p.xy;
+      const float tz = tau_p.z;
+      tau_p = P3{landed ? zero : txy, landed ? 0.0f : tz};
+      tau = v3(0.0f, 0.0f, 0.0f);   // (unused: the integrator takes tau_p)
+#endif
+    } else if constexpr (PLAIN) {
       // the landing radius as selects of the same values: no exec region between the controller and the integrator
       const bool landed = sqrtf(dot(dd, dd)) < tp.land_radius;
       S.land_flag = landed ? 1 : S.land_flag;
@@ -1096,12 +1135,22 @@ OUZ_DEV void env_core(const StepArgs& a, const StepCtx& sc, int i, uint32_t gid,
     const float h = c.dt / (float)c.substeps;   // (PLAIN too: the run-time quotient, loop invariant, not a folded one)
     // sim_params gravity (gym.set_sim_params after apply_randomizations, vec_task.py:648-660): nominal unless DR'd
     const V3 grav = (drn_mask & 4) ? gravity_dr(grav_dr_of(a.drn), a.seed, sc.step) : v3(0.0f, 0.0f, -kGravity);
-    M3* const R_out = CARRY ? Rc : nullptr;
+    if constexpr (form_packed(FORM, CTRL)) {
+#ifndef OUZ_HOST
+      P3 pp = p3(S.p), vp = p3(S.v), wp = p3(S.w);
+      PQ qp = pq(S.q);
+      integrate_thrust_body2<kRare>(pp, qp, vp, wp, *Rc, f_b.z, tau_p, inv_m, p3(I), p3(inv_I), h, c.wmax, deck, p3(grav), *Rc);
+      S.p = v3(pp); S.v = v3(vp); S.w = v3(wp); S.q = q4(qp);
+#endif
+    } else {
+    M3* R_out = nullptr;
+    if constexpr (CARRY) R_out = Rc;
     if (nsub == 2)   // the configured sub-step count (EKFLeeLanded.yaml:29), unrolled
       integrate_thrust_body<2, PLAIN, kRare>(S.p, S.q, S.v, S.w, R0, f_b.z, tau_b, inv_m, I, inv_I, h, c.wmax, deck, grav, 2, R_out);
     else
       integrate_thrust_body<0>(S.p, S.q, S.v, S.w, R0, f_b.z, tau_b, inv_m, I, inv_I, h, c.wmax, deck, grav, nsub,
                                R_out);
+    }
   }
 
   OUZ_STAMP(4, false);

@@ -322,9 +322,9 @@ __device__ __forceinline__ void run_env(const StepArgs& a, const StepCtx* ctx, i
     __builtin_amdgcn_s_waitcnt(kWaitVmcnt0);
     const bool fc0 = S.flags_clear, rst0 = S.rst;   // OWV: step 0's flag / reset state, for the output wave
     int out_seen = 0;                               // OWV: the output wave's consumed count last seen
-    M3 Rc{};                                        // CARRY: quat_to_mat of the state quaternion
+    CarryR<core_form(FORM), CTRL> Rc{};             // CARRY: quat_to_mat of the state quaternion
     if constexpr (CARRY) {
-      if (valid) Rc = quat_to_mat(S.q);             // the first step's, from the loaded state
+      if (valid) carry_set(Rc, S.q);                // the first step's, from the loaded state
     }
     for (int k = 0; k < K; ++k) {
       if (kStampSlots > 13 && k <= 16) OUZ_STAMP(13 + k, false);
@@ -1277,6 +1277,91 @@ __global__ void __launch_bounds__(64) philox_kernel(uint64_t seed, const uint32_
   out[i * 4] = r.x; out[i * 4 + 1] = r.y; out[i * 4 + 2] = r.z; out[i * 4 + 3] = r.w;
 }
 
+// The packed-pair forms (quad_math.h) beside the scalar forms they restate, on the same rows, for the bitwise test.
+// A row of OUZ_PACKED_PAIR_IN floats: a[3] b[3] c[3] qa[4] qb[4] s d[3] e[3] wmax fz h yaw_rate.  Both outputs get
+// OUZ_PACKED_PAIR_OUT floats per row in the same order: the primitives, then the three chain functions.
+template <bool PACKED>
+__device__ __forceinline__ void packed_pair_row(const float* r, float* o) {
+  int k = 0;
+  auto put = [&](float x) { o[k++] = x; };
+  const V3 a = v3(r[0], r[1], r[2]), b = v3(r[3], r[4], r[5]), c = v3(r[6], r[7], r[8]), d = v3(r[18], r[19], r[20]),
+           e = v3(r[21], r[22], r[23]);
+  const Q4 qa{r[9], r[10], r[11], r[12]}, qb{r[13], r[14], r[15], r[16]};
+  const float s = r[17], wmax = r[24], fz = r[25], h = r[26], yaw_rate = r[27];
+  const DeckContact deck{true, e.x, e.y, e.z, s};
+  const V3 I = v3(0.0347563f, 0.0458929f, 0.0977f), inv_I = v3(1.0f / 0.0347563f, 1.0f / 0.0458929f, 1.0f / 0.0977f);
+  const V3 grav = v3(0.0f, 0.0f, -kGravity);
+  if constexpr (!PACKED) {
+    auto put3 = [&](V3 x) { put(x.x); put(x.y); put(x.z); };
+    auto put4 = [&](Q4 x) { put(x.x); put(x.y); put(x.z); put(x.w); };
+    auto putm = [&](const M3& m) { for (int j = 0; j < 9; ++j) put(m.m[j]); };
+    const M3 M{{a.x, a.y, a.z, b.x, b.y, b.z, c.x, c.y, c.z}};
+    put3(a + b); put3(a - b); put3(s * a); put3(mul(a, b)); put3(cross(a, b)); put3(mv(M, d)); put3(mtv(M, d));
+    const M3 R = quat_to_mat(qa);
+    putm(R);
+    float us, uc;
+    unit2(a.x, b.x, us, uc); put(us); put(uc);
+    const EulerSC eu = euler_sc(M);
+    put(eu.sr); put(eu.cr); put(eu.sp); put(eu.cp); put(eu.sy); put(eu.cy);
+    put4(quat_mul(qa, qb));
+    put3(v3(2.0f * (qa.x * qa.z + qa.y * qa.w), 2.0f * (qa.y * qa.z - qa.x * qa.w), 1.0f - 2.0f * (qa.x * qa.x + qa.y * qa.y)));
+    const float qi = 1.0f / sqrtf(qb.x * qb.x + qb.y * qb.y + qb.z * qb.z + qb.w * qb.w);
+    put4(Q4{qb.x * qi, qb.y * qi, qb.z * qi, qb.w * qi});
+    const M3 Rd{{a.x, b.x, c.x, a.y, b.y, c.y, a.z, b.z, c.z}};
+    put3(lee_attitude_loop(R, Rd, d, euler_sc(quat_to_mat(qb)), yaw_rate, default_gains()));
+    float T;
+    V3 tau;
+    lee_position_R<true>(R, a, b, c, v3(0.0f, 0.0f, 1.0f), 0.0f, default_gains(), T, tau);
+    put(T); put3(tau);
+    V3 p = a, v = b, w = c;
+    Q4 q = qa;
+    M3 R1;
+    integrate_thrust_body<2, true, true>(p, q, v, w, R, fz, d, 0.7f, I, inv_I, h, wmax, deck, grav, 2, &R1);
+    put3(p); put4(q); put3(v); put3(w); putm(R1);
+  } else {
+    auto put3 = [&](P3 x) { put(x.xy.x); put(x.xy.y); put(x.z); };
+    auto put4 = [&](PQ x) { put(x.xy.x); put(x.xy.y); put(x.zw.x); put(x.zw.y); };
+    auto putm = [&](const PR& m) { put3(m.r0); put3(m.r1); put3(m.r2); };
+    const P3 pa = p3(a), pb = p3(b), pc = p3(c), pd = p3(d);
+    const PR M = pr(M3{{a.x, a.y, a.z, b.x, b.y, b.z, c.x, c.y, c.z}});
+    put3(pa + pb); put3(pa - pb); put3(s * pa); put3(mul(pa, pb)); put3(cross(pa, pb)); put3(mv(M, pd)); put3(mtv(M, pd));
+    const PR R = quat_to_mat(pq(qa));
+    putm(R);
+    F2 us, uc;
+    unit2(F2{a.x, a.x}, F2{b.x, b.x}, us, uc); put(us.x); put(uc.y);
+    const EulerSC eu = euler_sc(M);
+    put(eu.sr); put(eu.cr); put(eu.sp); put(eu.cp); put(eu.sy); put(eu.cy);
+    put4(quat_mul(pq(qa), pq(qb)));
+    put3(third_col(pq(qa)));
+    put4(normalise(pq(qb)));
+    put3(lee_attitude_loop(R, pa, pb, pc, pd, euler_sc(quat_to_mat(pq(qb))), yaw_rate, gains_p(default_gains())));
+    float T;
+    P3 tau;
+    lee_position_R(R, pa, pb, pc, 1.0f, gains_p(default_gains()), T, tau);
+    put(T); put3(tau);
+    P3 p = pa, v = pb, w = pc;
+    PQ q = pq(qa);
+    PR R1;
+    integrate_thrust_body2<true>(p, q, v, w, R, fz, pd, 0.7f, p3(I), p3(inv_I), h, wmax, deck, p3(grav), R1);
+    put3(p); put4(q); put3(v); put3(w); putm(R1);
+    // the column form of R1 is the row form's elements
+    o[k - 9] = R1.c0.xy.x; o[k - 8] = R1.c1.xy.x; o[k - 7] = R1.c2.xy.x; o[k - 6] = R1.c0.xy.y; o[k - 5] = R1.c1.xy.y;
+    o[k - 4] = R1.c2.xy.y; o[k - 3] = R1.c0.z; o[k - 2] = R1.c1.z; o[k - 1] = R1.c2.z;
+  }
+  static_assert(OUZ_PACKED_PAIR_OUT == 78, "the row layout above");
+  // (k == OUZ_PACKED_PAIR_OUT here)
+}
+
+// (a template, instantiated by the last function of this file: the kernels before it keep their place in the listing)
+template <int = 0>
+__global__ void __launch_bounds__(64) packed_pair_kernel(const float* in, float* scalar, float* packed, int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float* r = in + (size_t)i * OUZ_PACKED_PAIR_IN;
+  packed_pair_row<false>(r, scalar + (size_t)i * OUZ_PACKED_PAIR_OUT);
+  packed_pair_row<true>(r, packed + (size_t)i * OUZ_PACKED_PAIR_OUT);
+}
+
 }  // namespace ouz
 
 // ===========================================================================
@@ -2142,6 +2227,14 @@ int ouz_philox(uint64_t seed, const uint32_t* env_ids, uint32_t step, uint32_t s
   hipLaunchKernelGGL(philox_kernel, dim3(grid_for(n, 64)), dim3(64), 0, (hipStream_t)stream, seed, env_ids, step, stream_id, sub,
                      out4, n);
   OUZ_LAUNCH_CHECK("philox_kernel");
+  return OUZ_OK;
+}
+
+int ouz_packed_pair(const float* in, float* scalar, float* packed, int32_t n, void* stream) {
+  OUZ_CHECK_N("ouz_packed_pair");
+  if (!in || !scalar || !packed) return fail(OUZ_ERR_INVALID, "ouz_packed_pair: null pointer");
+  hipLaunchKernelGGL(packed_pair_kernel<>, dim3(grid_for(n, 64)), dim3(64), 0, (hipStream_t)stream, in, scalar, packed, n);
+  OUZ_LAUNCH_CHECK("packed_pair_kernel");
   return OUZ_OK;
 }
 

@@ -945,4 +945,206 @@ OUZ_HD void integrate_thrust_body(V3& p, Q4& q, V3& v, V3& w, const M3& R0, floa
   if (R_out) *R_out = R1;
 }
 
+#ifndef OUZ_HOST
+// ---------------------------------------------------------------------------
+// Packed-pair forms (device only; DESIGN.md §5.1, docs/HISTORY.md round 20)
+// ---------------------------------------------------------------------------
+// The plain LeeLanded rollout's state wave runs alone on its SIMD and is bound by its instruction count; a
+// v_pk_{mul,add,fma}_f32 does two f32 operations in one issue slot of that wave.  Here the 3-vector math of its
+// chain is laid out once as (x, y) pairs plus a scalar z, so that the element-wise work, the matrix-vector products
+// and Rd^T R go through packed instructions without re-pairing registers between them.
+// The rule that keeps the bits: every half of every packed operation is the scalar form's operation on the same
+// operands, and every expression below has the shape of the scalar source's (a * b + c inside one expression fuses
+// in both, a product stored and added later in neither).  Dot products, norms and cross products stay scalar: a dot
+// is one chain, and a cross needs the (y, z, x) rotation, which no aligned register pair holds.
+#define OUZ_PK __device__ __forceinline__
+typedef float F2 __attribute__((ext_vector_type(2)));
+struct P3 { F2 xy; float z; };
+struct PQ { F2 xy, zw; };                  // xyzw
+// R(q) by rows (r_i = (m[3i], m[3i+1]), m[3i+2]: what mtv and Rd^T R read) and by columns (c_j = (m[j], m[3+j]),
+// m[6+j]: what mv reads; c2 is the body z axis).  Each element is computed once; a consumer takes what it reads.
+struct PR { P3 r0, r1, r2, c0, c1, c2; };
+
+OUZ_PK P3 p3(V3 a) { return P3{F2{a.x, a.y}, a.z}; }
+OUZ_PK V3 v3(P3 a) { return V3{a.xy.x, a.xy.y, a.z}; }
+OUZ_PK PQ pq(Q4 a) { return PQ{F2{a.x, a.y}, F2{a.z, a.w}}; }
+OUZ_PK Q4 q4(PQ a) { return Q4{a.xy.x, a.xy.y, a.zw.x, a.zw.y}; }
+OUZ_PK P3 operator+(P3 a, P3 b) { return P3{a.xy + b.xy, a.z + b.z}; }
+OUZ_PK P3 operator-(P3 a, P3 b) { return P3{a.xy - b.xy, a.z - b.z}; }
+OUZ_PK P3 operator*(float s, P3 a) { return P3{s * a.xy, s * a.z}; }
+OUZ_PK P3 mul(P3 a, P3 b) { return P3{a.xy * b.xy, a.z * b.z}; }
+OUZ_PK float dot(P3 a, P3 b) { return a.xy.x * b.xy.x + a.xy.y * b.xy.y + a.z * b.z; }
+OUZ_PK float norm(P3 a) { return sqrtf(dot(a, a)); }
+OUZ_PK P3 cross(P3 a, P3 b) {
+  const float ax = a.xy.x, ay = a.xy.y, bx = b.xy.x, by = b.xy.y;
+  return P3{F2{ay * b.z - a.z * by, a.z * bx - ax * b.z}, ax * by - ay * bx};
+}
+// a v.x + b v.y + c v.z: mtv(A, v) of A's rows a, b, c; mv(A, v) of A's columns a, b, c
+OUZ_PK P3 lin3(P3 a, P3 b, P3 c, P3 v) {
+  const float vx = v.xy.x, vy = v.xy.y;
+  return P3{a.xy * vx + b.xy * vy + c.xy * v.z, a.z * vx + b.z * vy + c.z * v.z};
+}
+// v.x a + v.y b + v.z c: row i of Rd^T R from Rd's column i (v) and R's rows
+OUZ_PK P3 lin3l(P3 v, P3 a, P3 b, P3 c) {
+  const float vx = v.xy.x, vy = v.xy.y;
+  return P3{vx * a.xy + vy * b.xy + v.z * c.xy, vx * a.z + vy * b.z + v.z * c.z};
+}
+OUZ_PK P3 mtv(const PR& A, P3 v) { return lin3(A.r0, A.r1, A.r2, v); }
+OUZ_PK P3 mv(const PR& A, P3 v) { return lin3(A.c0, A.c1, A.c2, v); }
+
+// One-instruction helpers where the compiler does not fold a half-negation into the operand modifiers (it negates
+// the whole pair with a v_pk_add_f32 and blends the halves with moves).  Each is a fused multiply-add per half, as the
+// scalar source's a * b + c and a * b - c inside one expression are; neg_lo / neg_hi flip a sign bit exactly.
+// a b.x + (c.x, -c.y)
+OUZ_PK F2 pk_fma_bx_nhi(F2 a, F2 b, F2 c) {
+  F2 d;
+  __asm__("v_pk_fma_f32 %0, %1, %2, %3 op_sel_hi:[1,0,1] neg_hi:[0,0,1]" : "=v"(d) : "v"(a), "v"(b), "v"(c));
+  return d;
+}
+// a b.x + (-c.x, c.y)
+OUZ_PK F2 pk_fma_bx_nlo(F2 a, F2 b, F2 c) {
+  F2 d;
+  __asm__("v_pk_fma_f32 %0, %1, %2, %3 op_sel_hi:[1,0,1] neg_lo:[0,0,1]" : "=v"(d) : "v"(a), "v"(b), "v"(c));
+  return d;
+}
+// a.x a.y + (-c.x, c.x)
+OUZ_PK F2 pk_fma_xy_ncx(F2 a, F2 c) {
+  F2 d;
+  __asm__("v_pk_fma_f32 %0, %1, %1, %2 op_sel:[0,1,0] op_sel_hi:[0,1,0] neg_lo:[0,0,1]" : "=v"(d) : "v"(a), "v"(c));
+  return d;
+}
+
+// quat_to_mat: the off-diagonal pairs (m2, m5) and (m6, m7) share the products (j r, i r); (m1, m3) differ in the
+// sign of k r; (m0, m4) share k k.
+OUZ_PK PR quat_to_mat(PQ q) {
+  const float r = q.zw.y, i = q.xy.x, j = q.xy.y, k = q.zw.x;
+  const float two_s = 2.0f / (r * r + i * i + j * j + k * k);
+  const F2 ji = q.xy.yx;
+  const F2 t = ji * r;                                         // (j r, i r)
+  const F2 krp = q.zw * q.zw.yx;                               // (k r, r k): one value
+  const float kk = k * k;
+  const F2 m04 = 1.0f - two_s * (ji * ji + kk);                // (j j + k k, i i + k k)
+  const float m8 = 1.0f - two_s * (i * i + j * j);
+  const F2 m13 = two_s * pk_fma_xy_ncx(q.xy, krp);             // (i j - k r, i j + k r)
+  const F2 m25 = two_s * pk_fma_bx_nhi(q.xy, q.zw, t);         // (i k + j r, j k - i r)
+  const F2 m67 = two_s * pk_fma_bx_nlo(q.xy, q.zw, t);         // (i k - j r, j k + i r)
+  return PR{P3{F2{m04.x, m13.x}, m25.x}, P3{F2{m13.y, m04.y}, m25.y}, P3{m67, m8},
+            P3{F2{m04.x, m13.y}, m67.x}, P3{F2{m13.x, m04.y}, m67.y}, P3{m25, m8}};
+}
+OUZ_PK PR pr(const M3& R) {
+  return PR{P3{F2{R.m[0], R.m[1]}, R.m[2]}, P3{F2{R.m[3], R.m[4]}, R.m[5]}, P3{F2{R.m[6], R.m[7]}, R.m[8]},
+            P3{F2{R.m[0], R.m[3]}, R.m[6]}, P3{F2{R.m[1], R.m[4]}, R.m[7]}, P3{F2{R.m[2], R.m[5]}, R.m[8]}};
+}
+OUZ_PK M3 m3(const PR& R) {
+  return M3{{R.r0.xy.x, R.r0.xy.y, R.r0.z, R.r1.xy.x, R.r1.xy.y, R.r1.z, R.r2.xy.x, R.r2.xy.y, R.r2.z}};
+}
+
+// unit2 of two independent argument pairs, side by side: (s, c)[k] = unit2(y[k], x[k])
+OUZ_PK void unit2(F2 y, F2 x, F2& s, F2& c) {
+  const F2 h2 = x * x + y * y;
+  const F2 ih{1.0f / sqrtf(h2.x), 1.0f / sqrtf(h2.y)};
+  const F2 ys = y * ih, xc = x * ih;
+  s = F2{h2.x > 0.0f ? ys.x : 0.0f, h2.y > 0.0f ? ys.y : 0.0f};
+  c = F2{h2.x > 0.0f ? xc.x : 1.0f, h2.y > 0.0f ? xc.y : 1.0f};
+}
+OUZ_PK EulerSC euler_sc(const PR& R) {   // its two unit2 calls as one: (roll, yaw)
+  EulerSC e;
+  F2 s, c;
+  unit2(F2{R.r2.xy.y, R.r1.xy.x}, F2{R.r2.z, R.r0.xy.x}, s, c);
+  e.sr = s.x; e.cr = c.x;
+  e.sp = -R.r2.xy.x;
+  e.cp = sqrtf(fmaxf(0.0f, 1.0f - R.r2.xy.x * R.r2.xy.x));
+  e.sy = s.y; e.cy = c.y;
+  return e;
+}
+
+OUZ_PK PQ quat_mul(PQ a, PQ b) {
+  const float ax = a.xy.x, ay = a.xy.y, az = a.zw.x, aw = a.zw.y, bx = b.xy.x, by = b.xy.y, bz = b.zw.x, bw = b.zw.y;
+  const F2 cxy{ay * bz - az * by, az * bx - ax * bz};
+  return PQ{aw * b.xy + bw * a.xy + cxy, F2{aw * bz + bw * az + (ax * by - ay * bx), aw * bw - (ax * bx + ay * by + az * bz)}};
+}
+
+// third column of R(q) for the unit quaternion q (the integrator's, between sub-steps)
+OUZ_PK P3 third_col(PQ q) {
+  const F2 t = q.xy.yx * q.zw.y;   // (q.y q.w, q.x q.w)
+  return P3{2.0f * pk_fma_bx_nhi(q.xy, q.zw, t), 1.0f - 2.0f * (q.xy.x * q.xy.x + q.xy.y * q.xy.y)};   // q.xy q.z + (t.x, -t.y)
+}
+OUZ_PK PQ normalise(PQ q) {
+  const float qi = 1.0f / sqrtf(q.xy.x * q.xy.x + q.xy.y * q.xy.y + q.zw.x * q.zw.x + q.zw.y * q.zw.y);
+  return PQ{q.xy * qi, q.zw * qi};
+}
+
+struct LeeGainsP { P3 kP, kV, kR, kW; };
+OUZ_PK LeeGainsP gains_p(const LeeGains& g) { return LeeGainsP{p3(g.kP), p3(g.kV), p3(g.kR), p3(g.kW)}; }
+
+// lee_attitude_loop with Rd given by its columns b1, b2, b3
+OUZ_PK P3 lee_attitude_loop(const PR& R, P3 b1, P3 b2, P3 b3, P3 omega, const EulerSC& e, float yaw_rate,
+                             const LeeGainsP& g) {
+  const P3 A0 = lin3l(b1, R.r0, R.r1, R.r2), A1 = lin3l(b2, R.r0, R.r1, R.r2), A2 = lin3l(b3, R.r0, R.r1, R.r2);   // rows of Rd^T R
+  const P3 e_R{F2{0.5f * (A2.xy.y - A1.z), 0.5f * (A0.z - A2.xy.x)}, 0.5f * (A1.xy.x - A0.xy.y)};
+  const P3 wd{F2{-e.sp * yaw_rate, e.sr * e.cp * yaw_rate}, e.cr * e.cp * yaw_rate};
+  const P3 des = lin3(A0, A1, A2, wd);
+  const P3 act = mtv(R, omega);
+  const P3 e_w = act - des;
+  return P3{-g.kR.xy * e_R.xy - g.kW.xy * e_w.xy, -g.kR.z * e_R.z - g.kW.z * e_w.z};
+}
+
+// lee_position_R<true> for a command on the z axis, (0, 0, cmd_z), which is the plain LeeLanded rollout's hover point.
+// The x / y position error is written -p: the scalar build selects the 0 - p.x that feeds the gain's multiply as a
+// negated operand of that multiply (so p.x = +0 gives -0 there, not the subtraction's +0), and the packed build would
+// keep the subtraction; written as the negation, both evaluate (-p.x) kP.x.
+OUZ_PK void lee_position_R(const PR& R, P3 p, P3 v, P3 w, float cmd_z, const LeeGainsP& g, float& thrust, P3& torque) {
+  const EulerSC e = euler_sc(R);
+  P3 a = mul(g.kP, P3{-p.xy, cmd_z - p.z}) - mul(g.kV, v);
+  a.z += 1.0f;
+  thrust = a.xy.x * R.c2.xy.x + a.xy.y * R.c2.xy.y + a.z * R.c2.z;
+  const P3 b3 = (1.0f / norm(a)) * a;
+  P3 b2 = cross(b3, P3{F2{e.cy, e.sy}, 0.0f});
+  b2 = (1.0f / norm(b2)) * b2;
+  const P3 b1 = cross(b2, b3);
+  const float ya = 0.0f - atan2_bounded_f(R.r1.xy.x, R.r0.xy.x);
+  float yr = remainder_small_f(ya, kTwoPiF);
+  if (yr > kPiF) yr -= kTwoPiF;
+  torque = lee_attitude_loop(R, b1, b2, b3, w, e, yr, g);
+}
+
+// integrate_thrust_body<2, true, RARE_CLAMP> with its R_out
+template <bool RARE_CLAMP>
+OUZ_PK void integrate_thrust_body2(P3& p, PQ& q, P3& v, P3& w, const PR& R0, float fz, P3 tau_b, float inv_m, P3 I,
+                                    P3 inv_I, float h, float wmax, DeckContact deck, P3 g, PR& R_out) {
+  P3 wb = mtv(R0, w);
+  P3 z = R0.c2;
+  const float acc = fz * inv_m;
+#pragma unroll
+  for (int s = 0; s < 2; ++s) {
+    if (s == 1) OUZ_SUBSTEP_STAMP(5);
+    if (s > 0) z = third_col(q);
+    v = v + h * P3{z.xy * acc + g.xy, z.z * acc + g.z};
+    const P3 c = cross(wb, mul(I, wb));
+    wb = wb + h * mul(inv_I, tau_b - c);
+    float n2 = dot(wb, wb);
+    const bool over = n2 > wmax * wmax;
+    if (RARE_CLAMP ? __builtin_expect(over, 0) : over) { wb = (wmax / sqrtf(n2)) * wb; n2 = wmax * wmax; }
+    p = p + h * v;
+    if (deck.on) {
+      const F2 d = p.xy - F2{deck.px, deck.py};
+      if (d.x * d.x + d.y * d.y < kDeckRadius2 && p.z < kDeckZRest) {
+        p.z = kDeckZRest;
+        v = P3{F2{deck.vx, deck.vy}, fmaxf(v.z, 0.0f)};
+        wb = P3{F2{0.0f, 0.0f}, 0.0f};
+        n2 = 0.0f;
+      }
+    }
+    const float n = sqrtf(n2);
+    const float th = 0.5f * h * n, th2 = th * th;
+    const float sc = 0.5f * h * (1.0f - th2 * (1.0f / 6.0f));
+    const float co = 1.0f - 0.5f * th2 * (1.0f - th2 * (1.0f / 12.0f));
+    q = quat_mul(q, PQ{wb.xy * sc, F2{wb.z * sc, co}});
+    if (s == 1) q = normalise(q);   // once, after the last sub-step
+  }
+  R_out = quat_to_mat(q);
+  w = mv(R_out, wb);
+}
+#endif  // !OUZ_HOST
+
 }  // namespace ouz
