@@ -94,6 +94,12 @@ constexpr bool form_carry(unsigned form, int ctrl) { return OUZ_CARRY_R != 0 && 
 // LeeLanded gained with them at 4096 and at 8192 envs, QuadFault lost 4.5 % at both (docs/HISTORY.md round 18).
 constexpr bool form_rare(unsigned form, int ctrl) { return has(form, F_PLAIN) && ctrl == CTRL_LEE_TRUE; }
 constexpr bool form_write_through(unsigned form, int task) { return has(form, F_PLAIN) && task == OUZ_TASK_LEE_LANDED; }
+// The plain LeeLanded rollout's state wave alone: the idle lanes of a partial tile step a copy of its last valid env,
+// so the step is not an exec region (run_env; docs/HISTORY.md round 21).  -DOUZ_IDLE_COPY=0: an A/B build.
+#ifndef OUZ_IDLE_COPY
+#define OUZ_IDLE_COPY 1
+#endif
+constexpr bool form_idle_copy(unsigned form, int ctrl) { return OUZ_IDLE_COPY != 0 && has(form, F_OWV) && form_rare(form, ctrl); }
 // The plain LeeLanded rollout's state wave alone: its controller and integrator in the packed-pair forms of
 // quad_math.h, bit for bit the scalar forms' values (docs/HISTORY.md round 20).  Its carried R(q) is then a PR.
 #ifdef OUZ_HOST

@@ -211,24 +211,49 @@ __host__ __device__ constexpr bool plain_task(int task) {
 // they are in (a float4 row per lane needed a register quad per store, i.e. 16 moves per step), and the state
 // wave re-reads the consumed count only when the count it last saw does not cover the slot it is about to reuse.
 constexpr int kOutRing = 8;
-constexpr int kOutFields = 16;   // p.xyz, q.xyzw, v.xyz, w.xyz, target.xyz
+// Fields per form: p.xyz, q.xyzw, v.xyz, w.xyz, and for the goal tasks target.xyz.  A platform target of a plain launch
+// is launch-uniform -- S.plat is env_load's literal (0, 0), so the post-step target is (0 + plat_off_x, 0, 0.377) in
+// every lane and step -- and the output wave forms it itself (out_target) instead of reading three ring rows back.
+// That ring's meta word is the 14th [field][lane] row of the slot: 13 fields + meta leave as 7 ds_write2st64_b32.
+// -DOUZ_UNIFORM_TARGET=0: an A/B build that publishes the target in every form.
+#ifndef OUZ_UNIFORM_TARGET
+#define OUZ_UNIFORM_TARGET 1
+#endif
+constexpr int out_fields(unsigned form, int tgt) {
+  return OUZ_UNIFORM_TARGET != 0 && has(form, F_PLAIN) && tgt == TGT_PLATFORM ? 13 : 16;
+}
+template <int NF>
 struct OutRingLds {
-  float post[kOutRing][kOutFields][64];
+  static_assert(NF == 16);
+  float post[kOutRing][16][64];
   int32_t meta[kOutRing][64];     // progress << 4 | rst(step 0) << 3 | flags_clear(step 0) << 2 | time_out << 1 | reset
   int post_count;                 // steps published by the state wave
   int consumed;                   // steps read by the output wave
+  __device__ __forceinline__ void put_meta(int slot, uint32_t lane, int32_t m) { meta[slot][lane] = m; }
+  __device__ __forceinline__ int32_t get_meta(int slot, uint32_t lane) const { return meta[slot][lane]; }
 };
+template <>
+struct OutRingLds<13> {
+  float post[kOutRing][14][64];   // row 13: the meta word's bits
+  int post_count;
+  int consumed;
+  __device__ __forceinline__ void put_meta(int slot, uint32_t lane, int32_t m) { post[slot][13][lane] = __int_as_float(m); }
+  __device__ __forceinline__ int32_t get_meta(int slot, uint32_t lane) const { return __float_as_int(post[slot][13][lane]); }
+};
+// The post-step target of the 13-field ring, with env_core's expression (S.plat = (0, 0)), so a -0.0 offset cannot differ.
+__device__ __forceinline__ V3 out_target(const TaskParams& tp) { return v3(0.0f + tp.plat_off_x, 0.0f, 0.377f); }
 
-__device__ __forceinline__ void out_publish(OutRingLds& R, int k, int& seen, V3 p, Q4 q, V3 v, V3 w, V3 target,
+template <int NF>
+__device__ __forceinline__ void out_publish(OutRingLds<NF>& R, int k, int& seen, V3 p, Q4 q, V3 v, V3 w, V3 target,
                                             int32_t progress, bool rs, bool to, bool fc0, bool rst0) {
   if (k >= kOutRing && seen < k - kOutRing + 1) seen = split_wait(&R.consumed, k - kOutRing + 1);
   const int slot = k % kOutRing;
   const uint32_t lane = threadIdx.x & 63u;
-  const float f[kOutFields] = {p.x, p.y, p.z, q.x, q.y, q.z, q.w, v.x, v.y, v.z, w.x, w.y, w.z,
-                               target.x, target.y, target.z};
+  const float f[16] = {p.x, p.y, p.z, q.x, q.y, q.z, q.w, v.x, v.y, v.z, w.x, w.y, w.z,
+                       target.x, target.y, target.z};
 #pragma unroll
-  for (int j = 0; j < kOutFields; ++j) R.post[slot][j][lane] = f[j];
-  R.meta[slot][lane] = (progress << 4) | (rst0 ? 8 : 0) | (fc0 ? 4 : 0) | (to ? 2 : 0) | (rs ? 1 : 0);
+  for (int j = 0; j < NF; ++j) R.post[slot][j][lane] = f[j];
+  R.put_meta(slot, lane, (progress << 4) | (rst0 ? 8 : 0) | (fc0 ? 4 : 0) | (to ? 2 : 0) | (rs ? 1 : 0));
   split_publish(&R.post_count, k + 1);
 }
 
@@ -251,7 +276,7 @@ __device__ __forceinline__ void run_env(const StepArgs& a, const StepCtx* ctx, i
                                         size_t out_stride, float* wave_lds, int i, int e, bool valid, int task,
                                         bool direct = false, int stats_mode = 0, LaneStats* ls = nullptr,
                                         float* wrench = nullptr, SplitPvLds* spl_lds = nullptr,
-                                        OutRingLds* orl = nullptr) {
+                                        OutRingLds<out_fields(FORM, TGT)>* orl = nullptr) {
   static_assert(form_checked<FORM>());
   constexpr bool MULTI = has(FORM, F_MULTI), PRE = has(FORM, F_PRE), CLS = has(FORM, F_CLS), QLN = has(FORM, F_QLN),
                  SPW = has(FORM, F_SPW), OWV = has(FORM, F_OWV), PLAIN = has(FORM, F_PLAIN),
@@ -261,6 +286,11 @@ __device__ __forceinline__ void run_env(const StepArgs& a, const StepCtx* ctx, i
   // the env's outputs / statistics / state writes: every lane, or lane 0 of the quad
   const bool lead = QLN ? (threadIdx.x & 3u) == 0u : true;
   const bool vout = valid && lead;
+  // The lanes that load and step.  form_idle_copy: every lane, so that the step is no exec region: an idle lane of a
+  // partial tile was handed the tile's last valid env (step_body: i and e clamped), computes that env's values a
+  // second time, and stores nothing -- every state store and statistic below stays behind `vout`, the output wave
+  // keeps its own `valid`, and __any(rst) / the rare clamps see a duplicate of a lane that is there anyway.
+  const bool run = form_idle_copy(FORM, CTRL) ? true : valid;
   PvQl ql{};
   SplitLane spl{spl_lds, 0, threadIdx.x & 63u};
   static_assert(!SPW || CTRL == CTRL_LEE_EST, "the split form is the estimator rollout's");
@@ -285,7 +315,7 @@ __device__ __forceinline__ void run_env(const StepArgs& a, const StepCtx* ctx, i
     ep_cnt_old = ldi(S.T, OUZ_I_EP_CNT);
     ep_len_old = ldi(S.T, OUZ_I_EP_LEN);
   }
-  if (valid) env_load<CTRL, TGT, load_form(FORM)>(a, e, tp, S, ctx[0].actions);
+  if (run) env_load<CTRL, TGT, load_form(FORM)>(a, e, tp, S, ctx[0].actions);
   if constexpr (QLN) {
     if (valid) pv_lds_load(ql, [&](int f) { return ld(S.T, OUZ_F_PV_P + f); });
     ql_sync();
@@ -324,7 +354,7 @@ __device__ __forceinline__ void run_env(const StepArgs& a, const StepCtx* ctx, i
     int out_seen = 0;                               // OWV: the output wave's consumed count last seen
     CarryR<core_form(FORM), CTRL> Rc{};             // CARRY: quat_to_mat of the state quaternion
     if constexpr (CARRY) {
-      if (valid) carry_set(Rc, S.q);                // the first step's, from the loaded state
+      if (run) carry_set(Rc, S.q);                // the first step's, from the loaded state
     }
     for (int k = 0; k < K; ++k) {
       if (kStampSlots > 13 && k <= 16) OUZ_STAMP(13 + k, false);
@@ -336,10 +366,10 @@ __device__ __forceinline__ void run_env(const StepArgs& a, const StepCtx* ctx, i
       const bool flags_clear = vout && (k == 0 ? S.flags_clear : !did_reset);
       spl.k = k;
       V3 post_target = v3(0.0f, 0.0f, 0.0f);
-      if (valid)
+      if (run)
         env_core<CTRL, TGT, core_form(FORM)>(a, ctx[k], e, gid, task, S, ob, rew, rs, to, nullptr, &ql, &spl, &post_target, &Rc);
       if (kStampSlots > 13 && k == 8) OUZ_STAMP(30, false);
-      if (valid && k + 1 < K) load_actions<CTRL, TGT, actions_form(FORM)>(ctx[k + 1].actions, S, e);   // next step's row, before emit
+      if (run && k + 1 < K) load_actions<CTRL, TGT, actions_form(FORM)>(ctx[k + 1].actions, S, e);   // next step's row, before emit
       if constexpr (OWV) {   // (the reset counts of the trajectory log are the output wave's)
         out_publish(*orl, k, out_seen, S.p, S.q, S.v, S.w, post_target, S.progress, rs, to, fc0, rst0);
           if (kStampSlots > 13 && k == 8) OUZ_STAMP(31, false);
@@ -402,10 +432,10 @@ __device__ __forceinline__ void run_env(const StepArgs& a, const StepCtx* ctx, i
 // stores of run_env's one-wave loop, from the state wave's published post-step state; at the end the episode
 // fields and the fused statistics.  Same functions (obs_reward, emit / emit_env) on the same values: the
 // outputs are bitwise those of the one-wave rollout.
-template <unsigned FORM, bool WT>
+template <unsigned FORM, bool WT, int NF>
 __device__ __forceinline__ void out_wave(const StepArgs& a, const StepCtx* ctx, int K, const OutPtrs* outs,
                                          size_t out_stride, float* wave_lds, int i, int e, bool valid, int task,
-                                         int stats_mode, LaneStats* ls, OutRingLds& R) {
+                                         int stats_mode, LaneStats* ls, OutRingLds<NF>& R) {
   constexpr bool CLS = has(FORM, F_CLS), PLAIN = has(FORM, F_PLAIN);
   const TaskParams& tp = a.tp[tp_slot(task)];
   const uint32_t gid = a.env_offset + (uint32_t)e, lane = threadIdx.x & 63u;
@@ -425,13 +455,15 @@ __device__ __forceinline__ void out_wave(const StepArgs& a, const StepCtx* ctx, 
     split_wait(&R.post_count, k + 1);
     if (kStampSlots > 13 && k == 8) OUZ_STAMP(30, false);
     const int slot = k % kOutRing;
-    float f[kOutFields];
+    float f[16];
 #pragma unroll
-    for (int j = 0; j < kOutFields; ++j) f[j] = R.post[slot][j][lane];
-    const int32_t meta = R.meta[slot][lane];
+    for (int j = 0; j < NF; ++j) f[j] = R.post[slot][j][lane];
+    const int32_t meta = R.get_meta(slot, lane);
     split_publish(&R.consumed, k + 1);   // the values are in registers: the slot is free
-    const V3 p = v3(f[0], f[1], f[2]), v = v3(f[7], f[8], f[9]), w = v3(f[10], f[11], f[12]),
-             target = v3(f[13], f[14], f[15]);
+    const V3 p = v3(f[0], f[1], f[2]), v = v3(f[7], f[8], f[9]), w = v3(f[10], f[11], f[12]);
+    V3 target;
+    if constexpr (NF == 13) target = out_target(tp);
+    else target = v3(f[13], f[14], f[15]);
     const Q4 q = Q4{f[3], f[4], f[5], f[6]};
     const int32_t progress = meta >> 4;
     const bool rs = (meta & 1) != 0, to = (meta & 2) != 0;
@@ -715,7 +747,8 @@ __device__ __forceinline__ void step_body(const StepArgs& a, const StepCtx* ctx,
   const int sm = (MULTI && rst) ? rst->mode : 0;
   LaneStats ls{0.0, 0.0, 0.0};
   SplitPvLds* spl = nullptr;
-  OutRingLds* orl = nullptr;
+  constexpr int NF = out_fields(FORM, PLAIN ? task_tgt(TASK) : TGT_GOAL);
+  OutRingLds<NF>* orl = nullptr;
   if constexpr (SPW || OWV) {
     // Multi-wave rollouts, one workgroup per 64-slot tile: wave 0 steps the tile's envs; with SPW (the
     // estimator's trigger-class layout, quad_pv_split.h) wave 1 steps their PV covariance; with OWV the last
@@ -725,7 +758,7 @@ __device__ __forceinline__ void step_body(const StepArgs& a, const StepCtx* ctx,
       spl = &s_split;
     }
     if constexpr (OWV) {
-      __shared__ OutRingLds s_out;
+      __shared__ OutRingLds<NF> s_out;
       orl = &s_out;
     }
     if (threadIdx.x == 0) {
@@ -754,7 +787,14 @@ __device__ __forceinline__ void step_body(const StepArgs& a, const StepCtx* ctx,
     const int run_task = TASK == OUZ_TASK_MIXED ? chunk_task : TASK;
     constexpr int kOutRole = SPW ? 2 : 1;
     if (role == 0) {
-      if constexpr (TASK != OUZ_TASK_MIXED) OUZ_RUN_ENV(TASK, FORM, valid, false);
+      if constexpr (TASK != OUZ_TASK_MIXED && form_idle_copy(FORM, task_ctrl(TASK))) {
+        // an idle lane of a partial tile loads and steps a copy of the tile's last valid env (run_env: `run`)
+        const int il = min(i, a.n - 1);
+        {
+          const int i = il, e = il;
+          OUZ_RUN_ENV(TASK, FORM, valid, false);
+        }
+      } else if constexpr (TASK != OUZ_TASK_MIXED) OUZ_RUN_ENV(TASK, FORM, valid, false);
       else if constexpr (CLS) {
         OUZ_RUN_CHUNK(chunk_task, valid, OUZ_TASK_TRACKING, OUZ_TASK_LEE_LANDED, OUZ_TASK_FAULT);
       }
@@ -763,7 +803,7 @@ __device__ __forceinline__ void step_body(const StepArgs& a, const StepCtx* ctx,
       if (run_task == OUZ_TASK_TRACKING || run_task == OUZ_TASK_EKF_LEE_LANDED)
         cov_wave(a, ctx, K, i, e, valid, *spl);
     } else if (OWV && role == kOutRole) {
-      out_wave<FORM, form_write_through(FORM, TASK)>(a, ctx, K, outs, out_stride, wave_lds, i, e, valid, run_task, sm, &ls, *orl);
+      out_wave<FORM, form_write_through(FORM, TASK), NF>(a, ctx, K, outs, out_stride, wave_lds, i, e, valid, run_task, sm, &ls, *orl);
       if (sm) reduce_stats(*rst, blockIdx.x, gridDim.x, ls);   // the output waves of the exact grid
     }
     return;
