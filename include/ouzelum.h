@@ -32,6 +32,8 @@
  *                   storage rows, the statistics from a separate launch; bitwise K ouz_step calls.  The
  *                   fused launches agree with those within float tolerance (other code generation), so
  *                   results go from bitwise-equal-to-ouz_step to within-tolerance at that boundary.
+ *   ouz_policy_rollout  the learners' rollout loop itself for the MLP actor (PPO/main.py:85-96: getAction, envs.step,
+ *                   POMDP.observation, the storage writes) in launches of up to 32 steps
  *   ouz_pre_physics the task's pre_physics_step alone (ekf_lee_landed.py:308-530, lee_landed.py:263-330,
  *                   ouzelum.py:218-251): lazy reset, estimator / controller / guidance / thrust model, and the
  *                   body wrench handed to apply_rigid_body_force_tensors; no integration, no outputs, the
@@ -80,7 +82,8 @@ extern "C" {
                                   with no struct or signature changed: the running normalisation (ouz_moments_batch,
                                   ouz_moments_merge, ouz_normalize_rows, ouz_linear_tanh_small_k_norm), the value
                                   bootstrap (ouz_gae_bootstrap), the bounded atan2 beside the library's
-                                  (ouz_atan2_pair), the packed-pair forms beside the scalar ones (ouz_packed_pair) */
+                                  (ouz_atan2_pair), the packed-pair forms beside the scalar ones (ouz_packed_pair),
+                                  the fused rollout with the MLP policy in the loop (ouz_policy_rollout) */
 
 /* error codes */
 #define OUZ_OK 0
@@ -346,6 +349,65 @@ int ouz_episode_stats(ouz_env* env, double* out, int32_t drain, void* stream);
  * RPO-LSTM/main.py:96-110) for one host call per rollout instead of two. */
 int ouz_step_n_stats(ouz_env* env, const float* action_ring, int32_t ring_len, int32_t n_steps, double* stats_out,
                      int32_t drain, void* stream);
+
+/* The fused rollout with the policy in the loop (entry point added under ABI 9): n_steps env steps
+ * whose actions come from the 13 -> 256 -> 256 -> 4 tanh MLP actor (PPO/model.py:11-40), evaluated inside the
+ * rollout kernel, in launches of <= 32 steps like ouz_rollout.  Tasks: OUZ_TASK_OUZELUM, OUZ_TASK_FAULT and
+ * OUZ_TASK_LANDING (the tasks whose step takes an action); any other task is OUZ_ERR_INVALID.  Per step k:
+ *   x_k      the policy's input: act_in0 at k = 0, afterwards row k - 1 of pomdp_out (acts_on_pomdp != 0) or of
+ *            obs_out, through ouz_normalize_rows' FORWARD arithmetic when norm_m / norm_r are given;
+ *   mean     W3 tanh(W2 tanh(W1 x_k + b1) + b2) + b3, f32 (the 256 x 256 layer on the f32 MFMA);
+ *   eps      sample_mode 0: drawn in the kernel, the four normals of env g (global id) from ONE Philox block keyed
+ *            (sample_seed, g, sample_call0 + k, stream 9), Box-Muller pairs (x, y) -> eps 0, 1 and (z, w) -> eps 2, 3;
+ *            1: row k of eps_in; 2: zero (the mean action);
+ *   action   mean + exp(logstd) eps, stored UNclamped in action_out (what the learners store); the env clamps it;
+ *   logprob  -1/2 sum eps^2 - sum logstd - 4 log sqrt(2 pi), ouz_policy_sample's formula and summation order;
+ *   the env step with that action: the per-env code of ouz_rollout (lazy resets, DR noise, physical and gravity DR,
+ *            the trace), so obs_out / rew_out / reset_out / timeouts_out and the env state are bit for bit those of
+ *            ouz_rollout fed action_out as its ring; the env buffers receive the last step;
+ *   pomdp_out[k]  ouz_pomdp_obs(obs_out[k], pomdp_mode, pomdp_prob, pomdp_seed, pomdp_row_offset, pomdp_call0 + k),
+ *            bit for bit (the whole-batch flicker coins are drawn on the host).  May be null when pomdp_mode is
+ *            OUZ_POMDP_NONE (the policy then reads obs_out's rows whatever acts_on_pomdp says).
+ * A row's results depend on its global id only, not on its place in a 64-env tile or on the shard.  The env's step
+ * counter advances by n_steps.  stats_out: null, or the ouz_rollout_stats triple (drain as there; needs
+ * track_episodes).  All tensors f32 unless typed otherwise and contiguous; the weights, action_out, eps_in and
+ * eps_out 16-byte aligned, the 13-wide rows (act_in0, obs_out, pomdp_out) and the [K][N] buffers at their element
+ * alignment, as ouz_rollout's storage (so they may be rows 1.. of a (K + 1)-row tensor); eps_out may be null.  Like
+ * every launch function: stream-ordered, no synchronisation, no allocation.  The weights are read straight from the
+ * nn.Linear tensors ([out][in] row-major), so a bf16 form can later read other tensors without changing this ABI. */
+typedef struct ouz_policy_mlp {
+  const float *w1, *b1;                  /* [256][13], [256]  */
+  const float *w2, *b2;                  /* [256][256], [256] */
+  const float *w3, *b3;                  /* [4][256], [4]     */
+  const float* logstd;                   /* [4]               */
+  const float *norm_m, *norm_r;          /* [13] each, or both null: ouz_normalize_rows' forward constants */
+  float norm_clip;                       /* > 0 when the constants are given */
+} ouz_policy_mlp;
+
+typedef struct ouz_policy_rollout_io {
+  const float* act_in0;     /* [N][13]: what the policy is given at step 0 */
+  float* obs_out;           /* [K][N][13] env observation after each step (ouz_rollout's convention) */
+  float* pomdp_out;         /* [K][N][13] its learner-side corruption, or null when pomdp_mode == OUZ_POMDP_NONE */
+  float* action_out;        /* [K][N][4]  the sampled, unclamped action */
+  float* logprob_out;       /* [K][N] */
+  float* rew_out;           /* [K][N] */
+  int64_t* reset_out;       /* [K][N] */
+  uint8_t* timeouts_out;    /* [K][N] */
+  const float* eps_in;      /* [K][N][4], sample_mode 1 only */
+  float* eps_out;           /* [K][N][4] or null: the eps used */
+  int32_t acts_on_pomdp;    /* policy input after step k: pomdp row (1) or clean row (0) */
+  int32_t pomdp_mode;       /* OUZ_POMDP_*; prob / seed / row_offset / call as ouz_pomdp_obs takes them */
+  float pomdp_prob;
+  uint64_t pomdp_seed;
+  int64_t pomdp_row_offset;
+  uint32_t pomdp_call0;     /* the call index of step 0; step k is call pomdp_call0 + k */
+  int32_t sample_mode;      /* 0 drawn in the kernel, 1 given (eps_in), 2 the mean (eps = 0) */
+  uint64_t sample_seed;
+  uint32_t sample_call0;
+} ouz_policy_rollout_io;
+
+int ouz_policy_rollout(ouz_env* env, const ouz_policy_mlp* mlp, const ouz_policy_rollout_io* io, int32_t n_steps,
+                       double* stats_out, int32_t drain, void* stream);
 
 /* Per-step trace of one env + per-step reset counts, written by the step kernel
  * itself (no extra launch, no host sync).  Feeds the reference's trajectory CSV

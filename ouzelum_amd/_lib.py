@@ -110,6 +110,27 @@ class OuzEpisodeRecord(ctypes.Structure):   # ouz_episode_record, 16 bytes
     _fields_ = [("tag", ctypes.c_int32), ("env_id", ctypes.c_int32), ("ret", ctypes.c_float), ("len", ctypes.c_int32)]
 
 
+class OuzPolicyMlp(ctypes.Structure):   # ouz_policy_mlp: the nn.Linear tensors of the 13 -> 256 -> 256 -> 4 actor
+    _fields_ = [("w1", ctypes.c_void_p), ("b1", ctypes.c_void_p), ("w2", ctypes.c_void_p), ("b2", ctypes.c_void_p),
+                ("w3", ctypes.c_void_p), ("b3", ctypes.c_void_p), ("logstd", ctypes.c_void_p),
+                ("norm_m", ctypes.c_void_p), ("norm_r", ctypes.c_void_p), ("norm_clip", ctypes.c_float)]
+
+
+class OuzPolicyRolloutIo(ctypes.Structure):   # ouz_policy_rollout_io
+    _fields_ = [("act_in0", ctypes.c_void_p), ("obs_out", ctypes.c_void_p), ("pomdp_out", ctypes.c_void_p),
+                ("action_out", ctypes.c_void_p), ("logprob_out", ctypes.c_void_p), ("rew_out", ctypes.c_void_p),
+                ("reset_out", ctypes.c_void_p), ("timeouts_out", ctypes.c_void_p), ("eps_in", ctypes.c_void_p),
+                ("eps_out", ctypes.c_void_p), ("acts_on_pomdp", ctypes.c_int32), ("pomdp_mode", ctypes.c_int32),
+                ("pomdp_prob", ctypes.c_float), ("pomdp_seed", ctypes.c_uint64), ("pomdp_row_offset", ctypes.c_int64),
+                ("pomdp_call0", ctypes.c_uint32), ("sample_mode", ctypes.c_int32), ("sample_seed", ctypes.c_uint64),
+                ("sample_call0", ctypes.c_uint32)]
+
+
+POLICY_HIDDEN = 256       # the in-kernel actor's hidden width
+MAX_ROLLOUT_CHUNK = 32    # steps per launch of ouz_rollout / ouz_policy_rollout
+RNG_POLICY = 9            # philox.h RngStream: the in-kernel policy's Gaussian sample
+SAMPLE_DRAWN, SAMPLE_GIVEN, SAMPLE_MEAN = range(3)   # ouz_policy_rollout_io.sample_mode
+
 _P = ctypes.c_void_p
 _I = ctypes.c_int32
 _F = ctypes.c_float
@@ -143,6 +164,7 @@ SIGNATURES = {
     "ouz_reset_all": (_I, [_P, _P]),
     "ouz_episode_stats": (_I, [_P, _P, _I, _P]),
     "ouz_step_n_stats": (_I, [_P, _P, _I, _I, _P, _I, _P]),
+    "ouz_policy_rollout": (_I, [_P, ctypes.POINTER(OuzPolicyMlp), ctypes.POINTER(OuzPolicyRolloutIo), _I, _P, _I, _P]),
     "ouz_set_trace": (_I, [_P, _P, _P, _I, _I]),
     "ouz_set_dr_noise": (_I, [_P, _I, ctypes.POINTER(OuzDrNoise)]),
     "ouz_set_dr_physical": (_I, [_P, ctypes.POINTER(OuzDrPhysical)]),

@@ -2279,3 +2279,5 @@ int ouz_packed_pair(const float* in, float* scalar, float* packed, int32_t n, vo
 }
 
 }  // extern "C"
+
+#include "quad_policy.h"   // ouz_policy_rollout: the fused rollout with the MLP policy in the loop

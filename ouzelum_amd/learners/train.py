@@ -42,6 +42,13 @@ with the same flags loads its statistics and applies them without updating them.
 limit: the rollout then stores the env's ``time_outs`` beside the dones and GAE runs as ``ouz_gae_bootstrap``; the
 returned history carries ``timeout_frac``.  ``--max_episode_length N`` is the task YAML's ``maxEpisodeLength``.
 ``--play`` ignores ``--value_bootstrap``.
+
+``--fused_rollout`` (off by default) collects the rollout with ``FusedRollout``: one kernel launch per
+<= 32 steps that holds the env step, the learner-side corruption, the input normalisation, the MLP actor, the sample
+and the log-prob (``ouz_policy_rollout``).  For the MLP learners (PPO, RPO, PPO_Critic, RPO_Critic, ``--algo ppo``) on
+Ouzelum, QuadFault and Landing; refused otherwise.  The actions are drawn by the kernel's counter RNG (keyed by
+``--seed``, the global env id and the step), not by torch's generator, so a fused run is another sample of the same
+policy, reproducible and independent of the rank count.  ``--play --fused_rollout`` runs chunks of <= 32 steps.
 """
 import argparse
 import csv
@@ -115,7 +122,16 @@ def parse_args(argv=None):
                    help="GAE keeps gamma * V(terminal observation) where an episode ended by its time limit")
     p.add_argument("--max_episode_length", type=int, default=None,
                    help="the task YAML's maxEpisodeLength (default: the task's own)")
+    # the rollout as one launch per <= 32 steps with the MLP actor inside the kernel
+    p.add_argument("--fused_rollout", action="store_true",
+                   help="env step, corruption, normalisation, MLP actor and sample in one kernel (the MLP learners on "
+                        "Ouzelum / QuadFault / Landing); with --play: chunks of <= 32 steps")
     args = p.parse_args(argv)
+    if args.fused_rollout:
+        why = fused_rollout_refusal(VARIANTS[args.learner] if args.learner is not None
+                                    else legacy_variant(args.algo, args.rollout_obs), args.env)
+        if why:
+            p.error(why)
     if args.learner is not None:
         # given explicitly (their defaults say nothing): a second look at the same argv with no defaults
         probe = argparse.ArgumentParser(add_help=False)
@@ -295,6 +311,117 @@ class Rollout:
                                 self.next_done, self.init_state, self.logprobs, self.rewards, self.dones, **kw)
 
 
+FUSED_TASKS = ("Ouzelum", "QuadFault", "Landing")   # the tasks whose step takes the policy's action
+
+
+def fused_rollout_refusal(v, task):
+    """Why ``--fused_rollout`` cannot serve the row ``v`` on ``task`` (None: it can)."""
+    if v.recurrent:
+        return ("--fused_rollout evaluates the 13 -> 256 -> 256 -> 4 MLP actor inside the rollout kernel: it serves "
+                "PPO, RPO, PPO_Critic and RPO_Critic (and --algo ppo), not the LSTM learners")
+    if task not in FUSED_TASKS:
+        return (f"--fused_rollout needs a task whose step takes the policy's action ({', '.join(FUSED_TASKS)}), "
+                f"not {task}")
+    return None
+
+
+def actor_weights(agent):
+    """The MLP actor's tensors as ``QuadVecTask.policy_rollout_plan`` takes them (views: the optimiser updates them in
+    place)."""
+    m = agent.actor.actor_mean
+    return (m[0].weight, m[0].bias, m[2].weight, m[2].bias, m[4].weight, m[4].bias, agent.actor.actor_logstd.view(-1))
+
+
+class FusedRollout:
+    """``Rollout`` as ONE launch per <= 32 steps (``QuadVecTask.policy_rollout_plan``): the env step,
+    the learner-side corruption, the input normalisation, the MLP actor, the Gaussian sample and the log-prob all run
+    inside the rollout kernel.  The same attributes as ``Rollout`` (``update()`` is shared), held as views of
+    (T + 1)-row stores: row k is what came before step k, so ``obs = store[:T]``, ``next_obs = store[T]`` and row 0
+    of the next rollout is one copy of row T.  ``dones[k]``, ``timeouts[k]`` and the first clean observation of a run
+    follow ``Rollout``.  The episode statistics (``EpisodeRecorder``) are replayed after the launch from the stored
+    reward and done rows, of which they are a pure function; ``pomdp_w.calls`` advances by T, so a fused and a
+    per-step rollout can alternate.  The eps of env g at the rollout's step k is keyed (``sample_seed``, g,
+    ``sample_calls`` + k)."""
+
+    def __init__(self, envs, pomdp_w, agent, v, T, watch=False, sample_seed=0):
+        why = fused_rollout_refusal(v, envs.task_name)
+        if why:
+            raise ValueError(why)
+        self.envs, self.pomdp_w, self.agent, self.v, self.T = envs, pomdp_w, agent, v, T
+        self.single = single_stream(v)
+        self.recorder = envs if isinstance(envs, EpisodeRecorder) else None
+        N, device = agent.num_envs, agent.device
+        d = envs.observation_space.shape[0]
+        self._clean = torch.zeros((T + 1, N, d), device=device)
+        self._pomdp = torch.zeros((T + 1, N, d), device=device)
+        self._done = torch.zeros((T + 1, N), device=device)
+        self._tmo = torch.zeros((T + 1, N), dtype=torch.bool, device=device)
+        self._resets = torch.zeros((T, N), dtype=torch.int64, device=device)
+        self.actions = torch.zeros((T, N) + envs.action_space.shape, device=device)
+        self.logprobs = torch.zeros((T, N), device=device)
+        self.rewards = torch.zeros((T, N), device=device)
+        first = envs.reset()                     # the first observation of a run is the clean one in every routing
+        self._clean[0].copy_(first)
+        self._pomdp[0].copy_(first)
+        self.obs = (self._pomdp if self.single else self._clean)[:T]
+        self.pomdps = None if self.single else self._pomdp[:T]
+        self.dones = self._done[:T]
+        self.bootstrap = bool(getattr(agent, "value_bootstrap", False))
+        self.timeouts = self._tmo[:T] if self.bootstrap else None
+        self.next_timeout = self._tmo[T] if self.bootstrap else None
+        self.next_obs = (self._pomdp if self.single else self._clean)[T]
+        self.pomdp = self._pomdp[T]
+        self.next_done = self._done[T]
+        self.lstm_state = self.init_state = None
+        self.acts_on_pomdp = v.acts_on == "pomdp"
+        self.sample_calls = 0
+        self.seen = None
+        if watch:
+            self.seen = {"acted_on": (self._pomdp if self.acts_on_pomdp else self._clean)[:T], "dones": self._resets,
+                         "r": torch.zeros((T, N), device=device),
+                         "l": torch.zeros((T, N), dtype=torch.int32, device=device)}
+        norm = getattr(agent.actor, "obs_norm", None)
+        self._run = envs.policy_rollout_plan(
+            actor_weights(agent), T, (self._pomdp if self.acts_on_pomdp else self._clean)[0],
+            (self._clean[1:], self.rewards, self._resets, self._tmo[1:]), self.actions, self.logprobs,
+            pomdp=self._pomdp[1:], norm=None if norm is None else (norm.m, norm.r, norm.clip),
+            acts_on_pomdp=self.acts_on_pomdp, pomdp_mode=pomdp_w.mode, pomdp_prob=pomdp_w.prob,
+            pomdp_seed=pomdp_w.seed, pomdp_row_offset=pomdp_w.row_offset, sample_seed=sample_seed)
+        self._started = False
+
+    def collect(self, per_episode=False):
+        """T steps on from where the last call stopped, in ceil(T / 32) launches."""
+        T, rec = self.T, self.recorder
+        if self._started:   # row 0 of this rollout: what came after the last step of the previous one
+            store((self._clean[0], self._pomdp[0], self._done[0], self._tmo[0]),
+                  (self._clean[T], self._pomdp[T], self._done[T], self._tmo[T]))
+        self._started = True
+        self._run(self.pomdp_w.calls, self.sample_calls)
+        self.pomdp_w.calls += T
+        self.sample_calls += T
+        self._done[1:].copy_(self._resets)
+        if rec is not None:
+            if per_episode:
+                rec.begin_rollout()
+            for step in range(T):
+                if per_episode and step <= 2:
+                    rec.record(step)
+                rec.update(self.rewards[step], self._resets[step])
+                if self.seen is not None:
+                    store((self.seen["r"][step], self.seen["l"][step]),
+                          (rec.returned_episode_returns, rec.returned_episode_lengths))
+
+    update = Rollout.update
+
+
+def make_rollout(args, envs, pomdp_w, agent, v, T, watch=False):
+    """``Rollout``, or with ``--fused_rollout`` the one-launch ``FusedRollout`` (refused with its reason for the LSTM
+    learners and the tasks without a policy action)."""
+    if getattr(args, "fused_rollout", False):
+        return FusedRollout(envs, pomdp_w, agent, v, T, watch=watch, sample_seed=args.seed + 2)
+    return Rollout(envs, pomdp_w, agent, v, T, watch=watch)
+
+
 def train(args, on_rollout=None):
     """``on_rollout(dict)``, if given, is called once per rollout (after the update and the synchronize) with the
     rollout's tensors: ``obs`` and ``pomdps`` storage (``pomdps`` None for the single-stream learners), the bootstrap
@@ -319,7 +446,7 @@ def train(args, on_rollout=None):
                        rollout_steps=T, gemm_dtype=args.gemm_dtype, **learner_kwargs(args, v))
     name, best = run_names(args, v)
     num_updates = max(1, -(-args.total_steps // (T * N * world)))   # the loop's trips
-    ro = Rollout(envs, pomdp_w, agent, v, T, watch=on_rollout is not None)
+    ro = make_rollout(args, envs, pomdp_w, agent, v, T, watch=on_rollout is not None)
 
     writer = tb = None
     if rank == 0:
@@ -415,11 +542,39 @@ def play(args):
     tb = None
     if by_name:
         tb = EventWriter(os.path.join(args.logdir, names(v, args.POMDP, args.pomdp_prob)[0] + "_play"))
-    act_in = env.reset().clone()
-    next_done = torch.zeros(N, device=device)
-    lstm = agent.initial_state()
     rewards, global_step = [], 0
-    for _ in range(max(1, args.total_steps // N)):
+    if getattr(args, "fused_rollout", False):
+        # chunks of <= 32 steps, each one launch; the reward/play points from the stored reward rows
+        steps = max(1, args.total_steps // N)
+        acts = by_name and v.acts_on == "pomdp"
+        if not acts:
+            pomdp_w = POMDPWrapper("none", 0.0, seed=args.seed + 1)
+        v_play = v._replace(acts_on="pomdp" if acts else "clean", critic_on="clean")
+        ro = None
+        while steps > 0:
+            K = min(steps, 32)
+            if ro is None or ro.T != K:
+                prev = ro
+                ro = FusedRollout(env, pomdp_w, agent, v_play, K, sample_seed=args.seed + 2)
+                if prev is not None:   # carry on from the last chunk's final rows
+                    store((ro._clean[0], ro._pomdp[0]), (prev._clean[prev.T], prev._pomdp[prev.T]))
+                    ro.sample_calls = prev.sample_calls
+            ro.collect()
+            steps -= K
+            for r in ro.rewards.mean(1).tolist():
+                global_step += N
+                rewards.append(torch.tensor(r))
+                if tb is not None:
+                    tb.add_scalar("reward/play", r, global_step)
+                if not args.quiet:
+                    print((f"Step: {global_step}, " if by_name else "") + f"Average rewards {r:.4f}")
+        steps = 0
+    else:
+        steps = max(1, args.total_steps // N)
+        act_in = env.reset().clone()
+        next_done = torch.zeros(N, device=device)
+        lstm = agent.initial_state()
+    for _ in range(steps):
         global_step += N
         action, _, _, lstm = agent.act(act_in, lstm, next_done)
         act_in, rew, next_done, _ = env.step(action)

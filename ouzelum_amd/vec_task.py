@@ -55,6 +55,69 @@ def env_slots(task, n, env_id_offset=0):
     return out.astype(np.int64)
 
 
+def check_policy_rollout_args(n, n_steps, weights, act_in0, storage, actions, logprobs, pomdp=None, norm=None,
+                              pomdp_mode=L.POMDP_NONE, sample_mode=L.SAMPLE_DRAWN, eps_in=None, eps_out=None,
+                              device=None):
+    """The tensor checks of ``QuadVecTask.policy_rollout_plan`` for ``n`` envs (``ouz_policy_rollout``'s contract):
+    dtype, shape, contiguity and alignment (16 bytes for the weights, actions and eps) of every tensor, then, when ``device`` is given, that it lives on
+    that HIP device.  Raises before anything is launched."""
+    n, K = int(n), int(n_steps)
+    if K < 1:
+        raise ValueError("n_steps must be >= 1")
+    H = L.POLICY_HIDDEN
+
+    def one(t, name, shape, dtype=torch.float32, align=16):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name} must be a torch tensor")
+        if t.dtype != dtype:
+            raise ValueError(f"{name} must be {dtype} (got {t.dtype})")
+        if tuple(t.shape) != shape:
+            raise ValueError(f"{name} must have shape {shape} (got {tuple(t.shape)})")
+        if not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous")
+        if t.data_ptr() % align:
+            raise ValueError(f"{name} must be {align}-byte aligned")
+        if device is not None and t.device != device:
+            raise L.OuzelumError(f"{name} must be on {device} (got {t.device}); the HIP path has no CPU fallback")
+
+    if not isinstance(weights, (tuple, list)) or len(weights) != 7:
+        raise ValueError("weights must be (w1, b1, w2, b2, w3, b3, logstd)")
+    for t, name, shape in zip(weights, ("w1", "b1", "w2", "b2", "w3", "b3", "logstd"),
+                              ((H, L.NUM_OBS), (H,), (H, H), (H,), (L.NUM_ACT, H), (L.NUM_ACT,), (L.NUM_ACT,))):
+        one(t, name, shape)
+    if norm is not None:
+        if len(norm) != 3:
+            raise ValueError("norm must be (m, r, clip)")
+        one(norm[0], "norm m", (L.NUM_OBS,))
+        one(norm[1], "norm r", (L.NUM_OBS,))
+        if not float(norm[2]) > 0.0:
+            raise ValueError("norm clip must be > 0")
+    # (the 13-wide rows and the (K, N) buffers at their element alignment: they may be rows of a (K + 1)-row store)
+    one(act_in0, "act_in0", (n, L.NUM_OBS), align=4)
+    if not isinstance(storage, (tuple, list)) or len(storage) != 4:
+        raise ValueError("storage must be (obs, rew, reset, time_outs)")
+    one(storage[0], "storage obs", (K, n, L.NUM_OBS), align=4)
+    one(storage[1], "storage rew", (K, n), align=4)
+    one(storage[2], "storage reset", (K, n), torch.int64, align=8)
+    one(storage[3], "storage time_outs", (K, n), torch.bool, align=1)
+    one(actions, "actions", (K, n, L.NUM_ACT))
+    one(logprobs, "logprobs", (K, n), align=4)
+    if pomdp is not None:
+        one(pomdp, "pomdp", (K, n, L.NUM_OBS), align=4)
+    elif pomdp_mode != L.POMDP_NONE:
+        raise ValueError("a pomdp_mode other than none needs the pomdp tensor")
+    if pomdp_mode not in (L.POMDP_NONE, L.POMDP_FLICKER, L.POMDP_NOISE, L.POMDP_FLICKER_NOISE):
+        raise ValueError(f"unknown pomdp_mode {pomdp_mode}")
+    if sample_mode not in (L.SAMPLE_DRAWN, L.SAMPLE_GIVEN, L.SAMPLE_MEAN):
+        raise ValueError("sample_mode must be SAMPLE_DRAWN, SAMPLE_GIVEN or SAMPLE_MEAN")
+    if sample_mode == L.SAMPLE_GIVEN and eps_in is None:
+        raise ValueError("sample_mode SAMPLE_GIVEN needs eps_in")
+    if eps_in is not None:
+        one(eps_in, "eps_in", (K, n, L.NUM_ACT))
+    if eps_out is not None:
+        one(eps_out, "eps_out", (K, n, L.NUM_ACT))
+
+
 DRONE_ACTOR = "Drone"    # the drone actor's name in every drone task (ekf_lee_landed.py:242, ouzelum.py:158)
 _DR_DIST = {"gaussian": 1, "uniform": 2, "loguniform": 3}
 _DR_OP = {"additive": 0, "scaling": 1}
@@ -755,6 +818,72 @@ class QuadVecTask:
             if rc:
                 L.check(rc, "ouz_rollout_stats")
         return run
+
+    def policy_rollout_plan(self, weights, n_steps, act_in0, storage, actions, logprobs, pomdp=None, norm=None,
+                            acts_on_pomdp=None, pomdp_mode=None, pomdp_prob=0.0, pomdp_seed=0, pomdp_row_offset=0,
+                            sample_mode=L.SAMPLE_DRAWN, sample_seed=0, eps_in=None, eps_out=None, drain=True):
+        """A validated, pre-bound rollout with the MLP actor in the loop (``ouz_policy_rollout``):
+        ``n_steps`` env steps whose actions come from ``weights = (w1 (256,13), b1, w2 (256,256), b2, w3 (4,256), b3,
+        logstd (4,))``, the ``nn.Linear`` tensors of the 13 -> 256 -> 256 -> 4 tanh actor, in one launch per 32 steps.
+        ``act_in0 (N,13)`` is what the policy is given at step 0; ``storage`` is ``rollout()``'s ``(obs (K,N,13), rew,
+        reset int64, time_outs bool)``; ``actions (K,N,4)`` receives the sampled unclamped actions, ``logprobs (K,N)``
+        their log-probabilities, ``pomdp (K,N,13)`` the learner-side corruption of each observation
+        (``pomdp_mode`` a ``POMDP_IDS`` name, with ``pomdp_prob / pomdp_seed / pomdp_row_offset`` as ``ouz_pomdp_obs``
+        takes them).  ``acts_on_pomdp`` (default: whether ``pomdp`` is given) picks the policy's input after each
+        step.  ``norm = (m (13,), r (13,), clip)``: ``ouz_normalize_rows``' forward constants applied to that input.
+        ``sample_mode``: ``SAMPLE_DRAWN`` (in-kernel Philox normals keyed by ``sample_seed``, the global env id and
+        the call), ``SAMPLE_GIVEN`` (``eps_in (K,N,4)``) or ``SAMPLE_MEAN``; ``eps_out (K,N,4)`` receives the eps used.
+
+        Returns ``run(pomdp_call0=0, sample_call0=0, stats_out_ptr=None)``: one C call on torch's current stream of
+        the env device; step k is corruption call ``pomdp_call0 + k`` and sample call ``sample_call0 + k``.  The
+        tensors are read at every call (the optimiser updates the weights in place); the caller keeps them alive."""
+        if self._host:
+            raise NotImplementedError("policy_rollout is the HIP path's fused kernel; the host build steps with step()")
+        if not self.uses_actions or self.task == L.TASK_MIXED:
+            raise ValueError(f"policy_rollout: task {self.task_name} takes no policy action "
+                             "(Ouzelum, QuadFault and Landing do)")
+        mode = L.POMDP_NONE if pomdp_mode is None else (
+            POMDP_IDS[pomdp_mode] if isinstance(pomdp_mode, str) else int(pomdp_mode))
+        check_policy_rollout_args(self.num_envs, n_steps, weights, act_in0, storage, actions, logprobs, pomdp, norm,
+                                  mode, sample_mode, eps_in, eps_out, device=self.device)
+        if not 0 <= int(pomdp_row_offset) <= 0xFFFFFFFF - self.num_envs:
+            raise ValueError("pomdp_row_offset must be in [0, 2^32 - num_envs)")
+        mlp = L.OuzPolicyMlp(*(L.ptr(w) for w in weights), *((L.ptr(norm[0]), L.ptr(norm[1]), float(norm[2]))
+                                                             if norm is not None else (None, None, 0.0)))
+        io = L.OuzPolicyRolloutIo(
+            L.ptr(act_in0), L.ptr(storage[0]), L.ptr(pomdp), L.ptr(actions), L.ptr(logprobs), L.ptr(storage[1]),
+            L.ptr(storage[2]), L.ptr(storage[3]), L.ptr(eps_in), L.ptr(eps_out),
+            int(pomdp is not None if acts_on_pomdp is None else bool(acts_on_pomdp)), mode, float(pomdp_prob),
+            int(pomdp_seed) & 0xFFFFFFFFFFFFFFFF, int(pomdp_row_offset), 0, int(sample_mode),
+            int(sample_seed) & 0xFFFFFFFFFFFFFFFF, 0)
+        keep = (weights, act_in0, storage, actions, logprobs, pomdp, norm, eps_in, eps_out)
+        fn, env, k_c, dr_c, dev = L.lib.ouz_policy_rollout, self._env, int(n_steps), 1 if drain else 0, self._dev_index
+        track = bool(self.cfg.track_episodes)
+
+        def run(pomdp_call0=0, sample_call0=0, stats_out_ptr=None, _keep=keep):
+            if stats_out_ptr is not None and not track:
+                raise RuntimeError("create the env with track_episodes=True")
+            io.pomdp_call0 = int(pomdp_call0) & 0xFFFFFFFF
+            io.sample_call0 = int(sample_call0) & 0xFFFFFFFF
+            rc = fn(env, mlp, io, k_c, stats_out_ptr, dr_c, L.stream_ptr(dev))
+            if rc:
+                L.check(rc, "ouz_policy_rollout")
+        return run
+
+    def policy_rollout(self, weights, n_steps, act_in0, storage, actions, logprobs, pomdp_call0=0, sample_call0=0,
+                       stats_out=None, check=False, **kw):
+        """One ``policy_rollout_plan(...)`` built and run (see there).  ``stats_out``: a float64 device tensor of >= 3
+        that receives the episode statistics as ``rollout(stats_out=...)`` does.  ``check``: synchronise and
+        ``check_health()``."""
+        run = self.policy_rollout_plan(weights, n_steps, act_in0, storage, actions, logprobs, **kw)
+        if stats_out is not None:
+            if (not isinstance(stats_out, torch.Tensor) or stats_out.dtype != torch.float64 or stats_out.numel() < 3
+                    or not stats_out.is_contiguous() or stats_out.device != self.device):
+                raise ValueError("stats_out must be a contiguous float64 tensor of >= 3 on the env device")
+        run(pomdp_call0, sample_call0, L.ptr(stats_out))
+        if check:
+            torch.cuda.synchronize(self.device)
+            self.check_health()
 
     def reset(self):
         """vec_task.py:377-389: returns the current obs, does not touch the simulation."""
