@@ -34,6 +34,8 @@
  *                   results go from bitwise-equal-to-ouz_step to within-tolerance at that boundary.
  *   ouz_policy_rollout  the learners' rollout loop itself for the MLP actor (PPO/main.py:85-96: getAction, envs.step,
  *                   POMDP.observation, the storage writes) in launches of up to 32 steps
+ *   ouz_policy_rollout_lstm  the same for the recurrent actor (RPO-LSTM/main.py:92-103, model.py:34-70: get_states
+ *                   with the done-masked carry inside the launch)
  *   ouz_pre_physics the task's pre_physics_step alone (ekf_lee_landed.py:308-530, lee_landed.py:263-330,
  *                   ouzelum.py:218-251): lazy reset, estimator / controller / guidance / thrust model, and the
  *                   body wrench handed to apply_rigid_body_force_tensors; no integration, no outputs, the
@@ -83,7 +85,8 @@ extern "C" {
                                   ouz_moments_merge, ouz_normalize_rows, ouz_linear_tanh_small_k_norm), the value
                                   bootstrap (ouz_gae_bootstrap), the bounded atan2 beside the library's
                                   (ouz_atan2_pair), the packed-pair forms beside the scalar ones (ouz_packed_pair),
-                                  the fused rollout with the MLP policy in the loop (ouz_policy_rollout) */
+                                  the fused rollout with the MLP policy in the loop (ouz_policy_rollout) and with
+                                  the LSTM policy in the loop (ouz_policy_rollout_lstm) */
 
 /* error codes */
 #define OUZ_OK 0
@@ -408,6 +411,40 @@ typedef struct ouz_policy_rollout_io {
 
 int ouz_policy_rollout(ouz_env* env, const ouz_policy_mlp* mlp, const ouz_policy_rollout_io* io, int32_t n_steps,
                        double* stats_out, int32_t drain, void* stream);
+
+/* ouz_policy_rollout with the recurrent actor in the loop (learners/models.py LSTMActor: 13 -> 512 -> 256 tanh trunk,
+ * LSTM(256, 128), 128 -> 4 mean head).  Everything ouz_policy_rollout says about the env side, the corruption, x_k,
+ * eps, action, logprob, the alignment of io's tensors and the launch holds here unchanged; the policy of step k is
+ *   keep     0 where the done that came with x_k is set, else 1: done_in0 (nonzero = set) at k = 0, afterwards
+ *            reset_out[k - 1];
+ *   (h, c)   keep * the carry after step k - 1 (h_in / c_in at k = 0);
+ *   gates    tanh(W2 tanh(W1 x_k + b1) + b2) W_ih^T + (b_ih + b_hh) + h W_hh^T, torch's order i, f, g, o, all three
+ *            products on the f32 MFMA; c' = sig(f) c + sig(i) tanh(g), h' = sig(o) tanh(c') in ouz_lstm_seq_fwd's
+ *            arithmetic;
+ *   mean     W_head h' + b_head.
+ * h_out / c_out receive the carry after the last step WITHOUT that step's done applied: the next call's done_in0
+ * (the last row of reset_out) applies it.  The carry tensors are [N][128] f32, 16-byte aligned, done_in0 [N] f32;
+ * h_in != h_out and c_in != c_out. */
+typedef struct ouz_policy_lstm {
+  const float *w1, *b1;                  /* [512][13], [512]  */
+  const float *w2, *b2;                  /* [256][512], [256] */
+  const float *w_ih, *w_hh;              /* [512][256], [512][128]: nn.LSTM's weight_ih_l0 / weight_hh_l0 */
+  const float *b_ih, *b_hh;              /* [512] each        */
+  const float *w_head, *b_head;          /* [4][128], [4]     */
+  const float* logstd;                   /* [4]               */
+  const float *norm_m, *norm_r;          /* [13] each, or both null: ouz_normalize_rows' forward constants */
+  float norm_clip;                       /* > 0 when the constants are given */
+} ouz_policy_lstm;
+
+typedef struct ouz_policy_lstm_carry {
+  const float *h_in, *c_in;              /* [N][128] the carry the launch starts from */
+  const float* done_in0;                 /* [N] nonzero: zero env's carry before step 0 */
+  float *h_out, *c_out;                  /* [N][128] the carry after the last step */
+} ouz_policy_lstm_carry;
+
+int ouz_policy_rollout_lstm(ouz_env* env, const ouz_policy_lstm* lstm, const ouz_policy_lstm_carry* carry,
+                            const ouz_policy_rollout_io* io, int32_t n_steps, double* stats_out, int32_t drain,
+                            void* stream);
 
 /* Per-step trace of one env + per-step reset counts, written by the step kernel
  * itself (no extra launch, no host sync).  Feeds the reference's trajectory CSV

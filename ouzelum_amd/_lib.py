@@ -126,7 +126,22 @@ class OuzPolicyRolloutIo(ctypes.Structure):   # ouz_policy_rollout_io
                 ("sample_call0", ctypes.c_uint32)]
 
 
+class OuzPolicyLstm(ctypes.Structure):   # ouz_policy_lstm: LSTMActor's tensors (13 -> 512 -> 256, LSTM(256, 128), 128 -> 4)
+    _fields_ = [("w1", ctypes.c_void_p), ("b1", ctypes.c_void_p), ("w2", ctypes.c_void_p), ("b2", ctypes.c_void_p),
+                ("w_ih", ctypes.c_void_p), ("w_hh", ctypes.c_void_p), ("b_ih", ctypes.c_void_p),
+                ("b_hh", ctypes.c_void_p), ("w_head", ctypes.c_void_p), ("b_head", ctypes.c_void_p),
+                ("logstd", ctypes.c_void_p), ("norm_m", ctypes.c_void_p), ("norm_r", ctypes.c_void_p),
+                ("norm_clip", ctypes.c_float)]
+
+
+class OuzPolicyLstmCarry(ctypes.Structure):   # ouz_policy_lstm_carry
+    _fields_ = [("h_in", ctypes.c_void_p), ("c_in", ctypes.c_void_p), ("done_in0", ctypes.c_void_p),
+                ("h_out", ctypes.c_void_p), ("c_out", ctypes.c_void_p)]
+
+
 POLICY_HIDDEN = 256       # the in-kernel actor's hidden width
+POLICY_LSTM_TRUNK = (512, 256)   # the in-kernel recurrent actor's trunk widths
+POLICY_LSTM_HIDDEN = 128         # and its LSTM's hidden size
 MAX_ROLLOUT_CHUNK = 32    # steps per launch of ouz_rollout / ouz_policy_rollout
 RNG_POLICY = 9            # philox.h RngStream: the in-kernel policy's Gaussian sample
 SAMPLE_DRAWN, SAMPLE_GIVEN, SAMPLE_MEAN = range(3)   # ouz_policy_rollout_io.sample_mode
@@ -165,6 +180,8 @@ SIGNATURES = {
     "ouz_episode_stats": (_I, [_P, _P, _I, _P]),
     "ouz_step_n_stats": (_I, [_P, _P, _I, _I, _P, _I, _P]),
     "ouz_policy_rollout": (_I, [_P, ctypes.POINTER(OuzPolicyMlp), ctypes.POINTER(OuzPolicyRolloutIo), _I, _P, _I, _P]),
+    "ouz_policy_rollout_lstm": (_I, [_P, ctypes.POINTER(OuzPolicyLstm), ctypes.POINTER(OuzPolicyLstmCarry),
+                                     ctypes.POINTER(OuzPolicyRolloutIo), _I, _P, _I, _P]),
     "ouz_set_trace": (_I, [_P, _P, _P, _I, _I]),
     "ouz_set_dr_noise": (_I, [_P, _I, ctypes.POINTER(OuzDrNoise)]),
     "ouz_set_dr_physical": (_I, [_P, ctypes.POINTER(OuzDrPhysical)]),

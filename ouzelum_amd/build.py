@@ -11,7 +11,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 SRCS = [os.path.join(HERE, "csrc", "quad_kernels.hip"), os.path.join(HERE, "csrc", "learner_kernels.hip")]
 DEPS = [*SRCS, *(os.path.join(HERE, "csrc", h) for h in ("quad_math.h", "quad_env.h", "philox.h", "quad_pv_ql.h",
-                                                          "quad_pv_split.h", "quad_policy.h")),
+                                                          "quad_pv_split.h", "quad_policy.h", "quad_policy_lstm.h")),
         os.path.join(ROOT, "include", "ouzelum.h")]
 # the host build of the same step (make(sim_device="cpu"); include/ouzelum_host.h)
 HOST_SRC = os.path.join(HERE, "csrc", "quad_host.cpp")

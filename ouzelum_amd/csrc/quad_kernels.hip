@@ -2281,3 +2281,4 @@ int ouz_packed_pair(const float* in, float* scalar, float* packed, int32_t n, vo
 }  // extern "C"
 
 #include "quad_policy.h"   // ouz_policy_rollout: the fused rollout with the MLP policy in the loop
+#include "quad_policy_lstm.h"   // ouz_policy_rollout_lstm: the same with the LSTM policy in the loop

@@ -49,6 +49,10 @@ and the log-prob (``ouz_policy_rollout``).  For the MLP learners (PPO, RPO, PPO_
 Ouzelum, QuadFault and Landing; refused otherwise.  The actions are drawn by the kernel's counter RNG (keyed by
 ``--seed``, the global env id and the step), not by torch's generator, so a fused run is another sample of the same
 policy, reproducible and independent of the rank count.  ``--play --fused_rollout`` runs chunks of <= 32 steps.
+
+``--fused_lstm_rollout`` (off by default) is the same for the LSTM learners (PPO-LSTM, RPO-LSTM,
+RPO-LSTM_Critic, ``--algo rpo_lstm``) on the same tasks, with ``FusedLSTMRollout``: the trunk, the LSTM cell with its
+done-masked carry and the head run inside the kernel (``ouz_policy_rollout_lstm``).  Refused for the MLP learners.
 """
 import argparse
 import csv
@@ -126,12 +130,17 @@ def parse_args(argv=None):
     p.add_argument("--fused_rollout", action="store_true",
                    help="env step, corruption, normalisation, MLP actor and sample in one kernel (the MLP learners on "
                         "Ouzelum / QuadFault / Landing); with --play: chunks of <= 32 steps")
+    # the same with the recurrent actor inside the kernel
+    p.add_argument("--fused_lstm_rollout", action="store_true",
+                   help="env step, corruption, normalisation, LSTM actor (carry included) and sample in one kernel (the "
+                        "LSTM learners on Ouzelum / QuadFault / Landing); with --play: chunks of <= 32 steps")
     args = p.parse_args(argv)
-    if args.fused_rollout:
-        why = fused_rollout_refusal(VARIANTS[args.learner] if args.learner is not None
-                                    else legacy_variant(args.algo, args.rollout_obs), args.env)
-        if why:
-            p.error(why)
+    for flag, refusal in (("fused_rollout", fused_rollout_refusal), ("fused_lstm_rollout", fused_lstm_rollout_refusal)):
+        if getattr(args, flag):
+            why = refusal(VARIANTS[args.learner] if args.learner is not None
+                          else legacy_variant(args.algo, args.rollout_obs), args.env)
+            if why:
+                p.error(why)
     if args.learner is not None:
         # given explicitly (their defaults say nothing): a second look at the same argv with no defaults
         probe = argparse.ArgumentParser(add_help=False)
@@ -343,8 +352,10 @@ class FusedRollout:
     per-step rollout can alternate.  The eps of env g at the rollout's step k is keyed (``sample_seed``, g,
     ``sample_calls`` + k)."""
 
+    _refusal = staticmethod(fused_rollout_refusal)
+
     def __init__(self, envs, pomdp_w, agent, v, T, watch=False, sample_seed=0):
-        why = fused_rollout_refusal(v, envs.task_name)
+        why = self._refusal(v, envs.task_name)
         if why:
             raise ValueError(why)
         self.envs, self.pomdp_w, self.agent, self.v, self.T = envs, pomdp_w, agent, v, T
@@ -380,14 +391,25 @@ class FusedRollout:
             self.seen = {"acted_on": (self._pomdp if self.acts_on_pomdp else self._clean)[:T], "dones": self._resets,
                          "r": torch.zeros((T, N), device=device),
                          "l": torch.zeros((T, N), dtype=torch.int32, device=device)}
-        norm = getattr(agent.actor, "obs_norm", None)
-        self._run = envs.policy_rollout_plan(
-            actor_weights(agent), T, (self._pomdp if self.acts_on_pomdp else self._clean)[0],
-            (self._clean[1:], self.rewards, self._resets, self._tmo[1:]), self.actions, self.logprobs,
-            pomdp=self._pomdp[1:], norm=None if norm is None else (norm.m, norm.r, norm.clip),
-            acts_on_pomdp=self.acts_on_pomdp, pomdp_mode=pomdp_w.mode, pomdp_prob=pomdp_w.prob,
-            pomdp_seed=pomdp_w.seed, pomdp_row_offset=pomdp_w.row_offset, sample_seed=sample_seed)
+        self._make_plan(sample_seed)
         self._started = False
+
+    def _plan_args(self, sample_seed):
+        """The tensors and keywords both policy rollout plans take after the policy's own."""
+        T, pomdp_w = self.T, self.pomdp_w
+        norm = getattr(self.agent.actor, "obs_norm", None)
+        return ((T, (self._pomdp if self.acts_on_pomdp else self._clean)[0],
+                 (self._clean[1:], self.rewards, self._resets, self._tmo[1:]), self.actions, self.logprobs),
+                dict(pomdp=self._pomdp[1:], norm=None if norm is None else (norm.m, norm.r, norm.clip),
+                     acts_on_pomdp=self.acts_on_pomdp, pomdp_mode=pomdp_w.mode, pomdp_prob=pomdp_w.prob,
+                     pomdp_seed=pomdp_w.seed, pomdp_row_offset=pomdp_w.row_offset, sample_seed=sample_seed))
+
+    def _make_plan(self, sample_seed):
+        args, kw = self._plan_args(sample_seed)
+        self._run = self.envs.policy_rollout_plan(actor_weights(self.agent), *args, **kw)
+
+    def _launch(self):
+        self._run(self.pomdp_w.calls, self.sample_calls)
 
     def collect(self, per_episode=False):
         """T steps on from where the last call stopped, in ceil(T / 32) launches."""
@@ -396,7 +418,7 @@ class FusedRollout:
             store((self._clean[0], self._pomdp[0], self._done[0], self._tmo[0]),
                   (self._clean[T], self._pomdp[T], self._done[T], self._tmo[T]))
         self._started = True
-        self._run(self.pomdp_w.calls, self.sample_calls)
+        self._launch()
         self.pomdp_w.calls += T
         self.sample_calls += T
         self._done[1:].copy_(self._resets)
@@ -414,9 +436,73 @@ class FusedRollout:
     update = Rollout.update
 
 
+def fused_lstm_rollout_refusal(v, task):
+    """Why ``--fused_lstm_rollout`` cannot serve the row ``v`` on ``task`` (None: it can)."""
+    if not v.recurrent:
+        return ("--fused_lstm_rollout evaluates the 13 -> 512 -> 256 -> LSTM(128) -> 4 recurrent actor inside the "
+                "rollout kernel: it serves PPO-LSTM, RPO-LSTM and RPO-LSTM_Critic (and --algo rpo_lstm), not the MLP "
+                "learners (--fused_rollout serves those)")
+    if task not in FUSED_TASKS:
+        return (f"--fused_lstm_rollout needs a task whose step takes the policy's action ({', '.join(FUSED_TASKS)}), "
+                f"not {task}")
+    return None
+
+
+def lstm_actor_weights(agent):
+    """The LSTM actor's tensors as ``QuadVecTask.lstm_policy_rollout_plan`` takes them (views: the optimiser updates
+    them in place)."""
+    a = agent.actor
+    return (a.network[0].weight, a.network[0].bias, a.network[2].weight, a.network[2].bias, a.lstm.weight_ih_l0,
+            a.lstm.weight_hh_l0, a.lstm.bias_ih_l0, a.lstm.bias_hh_l0, a.actor_mean.weight, a.actor_mean.bias,
+            a.actor_logstd.view(-1))
+
+
+class FusedLSTMRollout(FusedRollout):
+    """``FusedRollout`` for the recurrent learners (``QuadVecTask.lstm_policy_rollout_plan``): the
+    trunk, the LSTM cell and the head run inside the rollout kernel, which carries (h, c) through the launch and
+    zeroes the carry of env b before step k where ``dones[k, b]`` is set, as ``LSTMActor.get_states`` does.
+    ``init_state`` is the carry the launch started from and ``lstm_state`` the one it left (the last step's done not
+    applied: the next launch, like the next ``act``, applies it).  Two (h, c) pairs alternate between rollouts, so the
+    update reads an ``init_state`` that no later launch has overwritten."""
+
+    _refusal = staticmethod(fused_lstm_rollout_refusal)
+
+    def _make_plan(self, sample_seed):
+        args, kw = self._plan_args(sample_seed)
+        agent, w = self.agent, lstm_actor_weights(self.agent)
+        self._carry = [agent.initial_state(), agent.initial_state()]
+        self._runs = []
+        for j in (0, 1):
+            (hi, ci), (ho, co) = self._carry[j], self._carry[1 - j]
+            self._runs.append(self.envs.lstm_policy_rollout_plan(w, (hi[0], ci[0], self._done[0], ho[0], co[0]),
+                                                                 *args, **kw))
+        self._flip = 0
+        self.lstm_state = self._carry[0]
+
+    def _launch(self):
+        j = self._flip
+        self.init_state = self._carry[j]
+        self._runs[j](self.pomdp_w.calls, self.sample_calls)
+        self.lstm_state = self._carry[1 - j]
+        self._flip = 1 - j
+
+    def adopt(self, prev):
+        """Carry on from where the rollout ``prev`` (of another length) stopped: its last rows, carry and call
+        count."""
+        store((self._clean[0], self._pomdp[0], self._done[0]), (prev._clean[prev.T], prev._pomdp[prev.T],
+                                                                prev._done[prev.T]))
+        store(self._carry[0], prev.lstm_state)
+        self._flip = 0
+        self.lstm_state = self._carry[0]
+        self.sample_calls = prev.sample_calls
+
+
 def make_rollout(args, envs, pomdp_w, agent, v, T, watch=False):
     """``Rollout``, or with ``--fused_rollout`` the one-launch ``FusedRollout`` (refused with its reason for the LSTM
-    learners and the tasks without a policy action)."""
+    learners and the tasks without a policy action), or with ``--fused_lstm_rollout`` its recurrent form
+    ``FusedLSTMRollout`` (refused for the MLP learners)."""
+    if getattr(args, "fused_lstm_rollout", False):
+        return FusedLSTMRollout(envs, pomdp_w, agent, v, T, watch=watch, sample_seed=args.seed + 2)
     if getattr(args, "fused_rollout", False):
         return FusedRollout(envs, pomdp_w, agent, v, T, watch=watch, sample_seed=args.seed + 2)
     return Rollout(envs, pomdp_w, agent, v, T, watch=watch)
@@ -543,8 +629,11 @@ def play(args):
     if by_name:
         tb = EventWriter(os.path.join(args.logdir, names(v, args.POMDP, args.pomdp_prob)[0] + "_play"))
     rewards, global_step = [], 0
-    if getattr(args, "fused_rollout", False):
-        # chunks of <= 32 steps, each one launch; the reward/play points from the stored reward rows
+    fused_cls = (FusedLSTMRollout if getattr(args, "fused_lstm_rollout", False)
+                 else FusedRollout if getattr(args, "fused_rollout", False) else None)
+    if fused_cls is not None:
+        # chunks of <= 32 steps, each one launch (the LSTM carry chained from chunk to chunk); the reward/play points
+        # from the stored reward rows
         steps = max(1, args.total_steps // N)
         acts = by_name and v.acts_on == "pomdp"
         if not acts:
@@ -555,8 +644,10 @@ def play(args):
             K = min(steps, 32)
             if ro is None or ro.T != K:
                 prev = ro
-                ro = FusedRollout(env, pomdp_w, agent, v_play, K, sample_seed=args.seed + 2)
-                if prev is not None:   # carry on from the last chunk's final rows
+                ro = fused_cls(env, pomdp_w, agent, v_play, K, sample_seed=args.seed + 2)
+                if prev is not None and fused_cls is FusedLSTMRollout:
+                    ro.adopt(prev)
+                elif prev is not None:   # carry on from the last chunk's final rows
                     store((ro._clean[0], ro._pomdp[0]), (prev._clean[prev.T], prev._pomdp[prev.T]))
                     ro.sample_calls = prev.sample_calls
             ro.collect()

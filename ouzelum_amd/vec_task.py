@@ -61,11 +61,21 @@ def check_policy_rollout_args(n, n_steps, weights, act_in0, storage, actions, lo
     """The tensor checks of ``QuadVecTask.policy_rollout_plan`` for ``n`` envs (``ouz_policy_rollout``'s contract):
     dtype, shape, contiguity and alignment (16 bytes for the weights, actions and eps) of every tensor, then, when ``device`` is given, that it lives on
     that HIP device.  Raises before anything is launched."""
-    n, K = int(n), int(n_steps)
-    if K < 1:
+    if int(n_steps) < 1:
         raise ValueError("n_steps must be >= 1")
     H = L.POLICY_HIDDEN
+    one = _tensor_check(device)
+    if not isinstance(weights, (tuple, list)) or len(weights) != 7:
+        raise ValueError("weights must be (w1, b1, w2, b2, w3, b3, logstd)")
+    for t, name, shape in zip(weights, ("w1", "b1", "w2", "b2", "w3", "b3", "logstd"),
+                              ((H, L.NUM_OBS), (H,), (H, H), (H,), (L.NUM_ACT, H), (L.NUM_ACT,), (L.NUM_ACT,))):
+        one(t, name, shape)
+    _check_policy_io(n, n_steps, act_in0, storage, actions, logprobs, pomdp, norm, pomdp_mode, sample_mode, eps_in,
+                     eps_out, device)
 
+
+def _tensor_check(device):
+    """``one(t, name, shape, dtype, align)`` of the policy rollouts' argument checks."""
     def one(t, name, shape, dtype=torch.float32, align=16):
         if not isinstance(t, torch.Tensor):
             raise TypeError(f"{name} must be a torch tensor")
@@ -79,12 +89,16 @@ def check_policy_rollout_args(n, n_steps, weights, act_in0, storage, actions, lo
             raise ValueError(f"{name} must be {align}-byte aligned")
         if device is not None and t.device != device:
             raise L.OuzelumError(f"{name} must be on {device} (got {t.device}); the HIP path has no CPU fallback")
+    return one
 
-    if not isinstance(weights, (tuple, list)) or len(weights) != 7:
-        raise ValueError("weights must be (w1, b1, w2, b2, w3, b3, logstd)")
-    for t, name, shape in zip(weights, ("w1", "b1", "w2", "b2", "w3", "b3", "logstd"),
-                              ((H, L.NUM_OBS), (H,), (H, H), (H,), (L.NUM_ACT, H), (L.NUM_ACT,), (L.NUM_ACT,))):
-        one(t, name, shape)
+
+def _check_policy_io(n, n_steps, act_in0, storage, actions, logprobs, pomdp, norm, pomdp_mode, sample_mode, eps_in,
+                     eps_out, device):
+    """The checks the MLP and the LSTM policy rollout share: everything but the policy's own tensors."""
+    n, K = int(n), int(n_steps)
+    if K < 1:
+        raise ValueError("n_steps must be >= 1")
+    one = _tensor_check(device)
     if norm is not None:
         if len(norm) != 3:
             raise ValueError("norm must be (m, r, clip)")
@@ -116,6 +130,32 @@ def check_policy_rollout_args(n, n_steps, weights, act_in0, storage, actions, lo
         one(eps_in, "eps_in", (K, n, L.NUM_ACT))
     if eps_out is not None:
         one(eps_out, "eps_out", (K, n, L.NUM_ACT))
+
+
+LSTM_WEIGHT_NAMES = ("w1", "b1", "w2", "b2", "w_ih", "w_hh", "b_ih", "b_hh", "w_head", "b_head", "logstd")
+
+
+def check_lstm_policy_rollout_args(n, weights, carry, device=None):
+    """The checks ``QuadVecTask.lstm_policy_rollout_plan`` adds to ``check_policy_rollout_args``'s
+    (``ouz_policy_rollout_lstm``'s contract): the eleven weight tensors of ``LSTMActor`` and the carry
+    ``(h_in, c_in, done_in0, h_out, c_out)``, in distinct from out."""
+    n = int(n)
+    T1, T2 = L.POLICY_LSTM_TRUNK
+    H = L.POLICY_LSTM_HIDDEN
+    one = _tensor_check(device)
+    if not isinstance(weights, (tuple, list)) or len(weights) != len(LSTM_WEIGHT_NAMES):
+        raise ValueError(f"weights must be ({', '.join(LSTM_WEIGHT_NAMES)})")
+    shapes = ((T1, L.NUM_OBS), (T1,), (T2, T1), (T2,), (4 * H, T2), (4 * H, H), (4 * H,), (4 * H,), (L.NUM_ACT, H),
+              (L.NUM_ACT,), (L.NUM_ACT,))
+    for t, name, shape in zip(weights, LSTM_WEIGHT_NAMES, shapes):
+        one(t, name, shape)
+    if not isinstance(carry, (tuple, list)) or len(carry) != 5:
+        raise ValueError("carry must be (h_in, c_in, done_in0, h_out, c_out)")
+    for t, name, shape in zip(carry, ("h_in", "c_in", "done_in0", "h_out", "c_out"),
+                              ((n, H), (n, H), (n,), (n, H), (n, H))):
+        one(t, name, shape, align=4 if name == "done_in0" else 16)
+    if carry[0].data_ptr() == carry[3].data_ptr() or carry[1].data_ptr() == carry[4].data_ptr():
+        raise ValueError("the carry's in and out tensors must be distinct")
 
 
 DRONE_ACTOR = "Drone"    # the drone actor's name in every drone task (ekf_lee_landed.py:242, ouzelum.py:158)
@@ -876,6 +916,68 @@ class QuadVecTask:
         that receives the episode statistics as ``rollout(stats_out=...)`` does.  ``check``: synchronise and
         ``check_health()``."""
         run = self.policy_rollout_plan(weights, n_steps, act_in0, storage, actions, logprobs, **kw)
+        if stats_out is not None:
+            if (not isinstance(stats_out, torch.Tensor) or stats_out.dtype != torch.float64 or stats_out.numel() < 3
+                    or not stats_out.is_contiguous() or stats_out.device != self.device):
+                raise ValueError("stats_out must be a contiguous float64 tensor of >= 3 on the env device")
+        run(pomdp_call0, sample_call0, L.ptr(stats_out))
+        if check:
+            torch.cuda.synchronize(self.device)
+            self.check_health()
+
+    def lstm_policy_rollout_plan(self, weights, carry, n_steps, act_in0, storage, actions, logprobs, pomdp=None,
+                                 norm=None, acts_on_pomdp=None, pomdp_mode=None, pomdp_prob=0.0, pomdp_seed=0,
+                                 pomdp_row_offset=0, sample_mode=L.SAMPLE_DRAWN, sample_seed=0, eps_in=None,
+                                 eps_out=None, drain=True):
+        """``policy_rollout_plan`` with the recurrent actor in the loop (``ouz_policy_rollout_lstm``).
+        ``weights = (w1 (512,13), b1, w2 (256,512), b2, w_ih (512,256), w_hh (512,128), b_ih, b_hh, w_head (4,128),
+        b_head, logstd (4,))``: ``LSTMActor``'s tensors.  ``carry = (h_in (N,128), c_in, done_in0 (N,) f32, h_out,
+        c_out)``: the carry of env b is zeroed before step 0 where ``done_in0[b]`` is nonzero and before step k + 1
+        where step k's reset flag is set; ``h_out`` / ``c_out`` receive the carry after the last step without that
+        step's done applied (the next call's ``done_in0`` applies it).  In and out are distinct tensors.  Everything
+        else, and the returned ``run``, as ``policy_rollout_plan``."""
+        if self._host:
+            raise NotImplementedError("lstm_policy_rollout is the HIP path's fused kernel; the host build steps with "
+                                      "step()")
+        if not self.uses_actions or self.task == L.TASK_MIXED:
+            raise ValueError(f"lstm_policy_rollout: task {self.task_name} takes no policy action "
+                             "(Ouzelum, QuadFault and Landing do)")
+        mode = L.POMDP_NONE if pomdp_mode is None else (
+            POMDP_IDS[pomdp_mode] if isinstance(pomdp_mode, str) else int(pomdp_mode))
+        check_lstm_policy_rollout_args(self.num_envs, weights, carry, device=self.device)
+        _check_policy_io(self.num_envs, n_steps, act_in0, storage, actions, logprobs, pomdp, norm, mode, sample_mode,
+                         eps_in, eps_out, self.device)
+        if not 0 <= int(pomdp_row_offset) <= 0xFFFFFFFF - self.num_envs:
+            raise ValueError("pomdp_row_offset must be in [0, 2^32 - num_envs)")
+        lstm = L.OuzPolicyLstm(*(L.ptr(w) for w in weights), *((L.ptr(norm[0]), L.ptr(norm[1]), float(norm[2]))
+                                                               if norm is not None else (None, None, 0.0)))
+        cr = L.OuzPolicyLstmCarry(*(L.ptr(t) for t in carry))
+        io = L.OuzPolicyRolloutIo(
+            L.ptr(act_in0), L.ptr(storage[0]), L.ptr(pomdp), L.ptr(actions), L.ptr(logprobs), L.ptr(storage[1]),
+            L.ptr(storage[2]), L.ptr(storage[3]), L.ptr(eps_in), L.ptr(eps_out),
+            int(pomdp is not None if acts_on_pomdp is None else bool(acts_on_pomdp)), mode, float(pomdp_prob),
+            int(pomdp_seed) & 0xFFFFFFFFFFFFFFFF, int(pomdp_row_offset), 0, int(sample_mode),
+            int(sample_seed) & 0xFFFFFFFFFFFFFFFF, 0)
+        keep = (weights, carry, act_in0, storage, actions, logprobs, pomdp, norm, eps_in, eps_out)
+        fn, env, k_c, dr_c, dev = (L.lib.ouz_policy_rollout_lstm, self._env, int(n_steps), 1 if drain else 0,
+                                   self._dev_index)
+        track = bool(self.cfg.track_episodes)
+
+        def run(pomdp_call0=0, sample_call0=0, stats_out_ptr=None, _keep=keep):
+            if stats_out_ptr is not None and not track:
+                raise RuntimeError("create the env with track_episodes=True")
+            io.pomdp_call0 = int(pomdp_call0) & 0xFFFFFFFF
+            io.sample_call0 = int(sample_call0) & 0xFFFFFFFF
+            rc = fn(env, lstm, cr, io, k_c, stats_out_ptr, dr_c, L.stream_ptr(dev))
+            if rc:
+                L.check(rc, "ouz_policy_rollout_lstm")
+        return run
+
+    def lstm_policy_rollout(self, weights, carry, n_steps, act_in0, storage, actions, logprobs, pomdp_call0=0,
+                            sample_call0=0, stats_out=None, check=False, **kw):
+        """One ``lstm_policy_rollout_plan(...)`` built and run (see there); ``stats_out`` and ``check`` as
+        ``policy_rollout``."""
+        run = self.lstm_policy_rollout_plan(weights, carry, n_steps, act_in0, storage, actions, logprobs, **kw)
         if stats_out is not None:
             if (not isinstance(stats_out, torch.Tensor) or stats_out.dtype != torch.float64 or stats_out.numel() < 3
                     or not stats_out.is_contiguous() or stats_out.device != self.device):

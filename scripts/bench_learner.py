@@ -7,6 +7,7 @@ PPO update of 4 epochs x 2 minibatches) and splits wall time into rollout and up
     python scripts/bench_learner.py --env QuadFault --num_envs 8192 --gemm_dtype bf16
     python scripts/bench_learner.py --env QuadFault --num_envs 8192 --ent_coef 0.01 --clip_vloss
     python scripts/bench_learner.py --env QuadFault --num_envs 8192 --learner PPO --fused_rollout
+    python scripts/bench_learner.py --env QuadFault --num_envs 8192 --learner RPO-LSTM --fused_lstm_rollout
 
 The rollout is train.py's (``learners.train.Rollout``).  ``--algo`` times it on the bare env, with no episode
 bookkeeping; ``--learner NAME`` in NAME's routing (learners/variants.py) with the bookkeeping train.py has, one
@@ -23,7 +24,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from ouzelum_amd.learners import ExtractObsWrapper, POMDPWrapper, PPOLearner  # noqa: E402
-from ouzelum_amd.learners.train import FusedRollout, Rollout  # noqa: E402
+from ouzelum_amd.learners.train import FusedLSTMRollout, FusedRollout, Rollout  # noqa: E402
 from ouzelum_amd.learners.variants import LEARNERS, VARIANTS, legacy_variant  # noqa: E402
 from ouzelum_amd.learners.wrappers import EpisodeRecorder  # noqa: E402
 from ouzelum_amd.vec_task import make  # noqa: E402
@@ -44,6 +45,8 @@ ap.add_argument("--num_minibatches", type=int, default=2)
 ap.add_argument("--value_bootstrap", action="store_true")
 ap.add_argument("--fused_rollout", action="store_true",
                 help="train.py --fused_rollout: the rollout as one launch with the MLP actor in the kernel")
+ap.add_argument("--fused_lstm_rollout", action="store_true",
+                help="train.py --fused_lstm_rollout: the same with the LSTM actor in the kernel")
 a = ap.parse_args()
 v = VARIANTS[a.learner] if a.learner else legacy_variant(a.algo, "clean")
 per_episode = a.learner is not None and a.episode_log == "per_episode"
@@ -60,9 +63,10 @@ agent = PPOLearner(base.observation_space, base.action_space, N, dev, recurrent=
                    **({"value_bootstrap": True} if a.value_bootstrap else {}))
 options = {k: getattr(a, k) for k, d in (("ent_coef", 0.0), ("clip_vloss", False), ("update_epochs", 4),
                                          ("num_minibatches", 2), ("value_bootstrap", False),
-                                         ("fused_rollout", False))
+                                         ("fused_rollout", False), ("fused_lstm_rollout", False))
            if getattr(a, k) != d}   # the ones given
-ro = (FusedRollout if a.fused_rollout else Rollout)(env, POMDPWrapper("flicker", 0.1, seed=1), agent, v, T)
+ro = (FusedLSTMRollout if a.fused_lstm_rollout else FusedRollout if a.fused_rollout else Rollout)(
+    env, POMDPWrapper("flicker", 0.1, seed=1), agent, v, T)
 t_roll = t_upd = 0.0
 n_records = 0
 for it in range(a.warmup + a.iters):
